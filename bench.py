@@ -18,11 +18,20 @@ rollout then stays in, so a short window right after the reset would measure a p
 
 Rank 0 prints ONE JSON line: the contract keys plus
   roofline      HBM view of the step kernel (algorithmic bytes / HIP-event kernel time of this run)
+and, with --full only (each of these takes runs of its own after the timed window):
   roofline_valu fp64 vector-ALU view of the same kernel (the resource that actually binds): the flops the
                 kernel executed in THIS run's timed window -- its work counted by replaying the window from a
                 checkpoint with the counting variant of the kernel (same arithmetic, bit for bit), priced by
                 profiles/flop_model.json (per-unit flops fitted to rocprofv3 PMC counts) -- over the kernel time
+  rollout       the open-loop rollout line (K env-steps per launch), N=1 only
+  gym_level     env-steps/s through HipRuntime.step, the surface users call, N=1 only
   cpu_baseline  the CPU oracle (scalar fp64 port) timed on this box's host cores, N=1 only
+
+--dump-outputs DIR writes what the timed path computed in its last step -- the arrays an env.step caller receives:
+obs, reward, done (the flag bits), terminal_obs, of rank 0's environments (with --gather-obs: obs, reward, done as rank 0
+gathered them) -- as DIR/<name>.npy (float64 in f64, float32 in f32; done as float32).  The timed launches write into the handle's scratch buffers, so the last step is recomputed
+from a checkpoint taken before the window (the rollout is deterministic) and checked bit for bit against the state
+the timed window left.  Above 64 MB in all, a fixed seeded sample of the environments is written (env_index.npy).
 """
 import argparse
 import contextlib
@@ -39,6 +48,9 @@ if ROOT not in sys.path:
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
 FP64_VECTOR_PEAK_TF = 78.6     # MI355X fp64 vector peak (half the 157.3 TF fp32 vector rate)
 FP32_VECTOR_PEAK_TF = 157.3
+# untimed steps kept in flight from the checkpoint to the opening bracket of the timed window (see main)
+BUSY_STEPS = 40
+DUMP_LIMIT_BYTES = 64 << 20    # --dump-outputs: at most this much in all
 
 WORKLOADS = {
     # name: (task_mode, reward, contact, domain randomisation, description)
@@ -257,6 +269,64 @@ def load_json(name):
     return None
 
 
+def rewind(sim, ck, dr):
+    """Put a handle back where checkpoint `ck` was taken (its parameters only with domain randomisation: restoring them
+    would switch a nominal handle to per-env ones)."""
+    sim.set_state(ck["q"], ck["qd"])
+    if "solver_lambda" in ck:
+        sim.set_solver_state(ck["solver_lambda"], ck["solver_flags"])
+    sim.set_action_history(0, ck["hist0"]); sim.set_action_history(1, ck["hist1"])
+    if dr:
+        for f, v in ck["params"].items():
+            sim.set_params(f, v)
+    sim.set_episode_info(ck["steps"], ck["episode"], ck["pose"])
+    sim.step_count = ck["step_count"]
+
+
+def last_step_outputs(sims, streams, cks, ends, dr, skip):
+    """The outputs of the last timed step of every shard, recomputed: rewind to the checkpoint taken before the window,
+    enqueue the `skip` steps that lay between it and the last timed step the way the timed path did, then make that last
+    step into caller tensors.  The state it leaves must equal `ends`, the state the timed window left, bit for bit.
+    -> {name: numpy array over the shards' environments in order}."""
+    import numpy as np
+    import torch
+    parts = []
+    for i, (sim, ck) in enumerate(zip(sims, cks)):
+        rewind(sim, ck, dr)
+        with (torch.cuda.stream(streams[i]) if streams[i] is not None else contextlib.nullcontext()):
+            if skip > 0:
+                sim.bench_enqueue(skip)
+            obs, rew, done = sim._new(sim.N, sim.D), sim._new(sim.N), sim._new(sim.N, dtype=torch.uint8)
+            term = sim._new(sim.N, sim.D)
+            sim.step_into(None, obs, rew, done, term)
+        torch.cuda.synchronize()
+        q, qd = sim.get_state()
+        if not (torch.equal(q, ends[i][0]) and torch.equal(qd, ends[i][1]) and sim.step_count == ends[i][2]):
+            raise SystemExit(f"--dump-outputs: the replay of shard {i} does not reach the state the timed window left")
+        parts.append((obs, rew, done, term))
+    np_dtype = np.float64 if sims[0].dtype == torch.float64 else np.float32
+    names = ("obs", "reward", "done", "terminal_obs")
+    return {nm: np.concatenate([p[k].cpu().numpy() for p in parts]).astype(np_dtype if nm != "done" else np.float32)
+            for k, nm in enumerate(names)}
+
+
+def write_outputs(out_dir, arrays, seed):
+    """DIR/<name>.npy for every array (float32 / float64); above DUMP_LIMIT_BYTES, the rows of a fixed seeded sample of the
+    environments (all arrays are indexed by environment along their first axis), with their indices in env_index.npy."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    n = len(next(iter(arrays.values())))
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        per_env = total / n + 8                       # (+ the index column)
+        idx = np.sort(np.random.default_rng(seed).choice(n, int(DUMP_LIMIT_BYTES // per_env), replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+        arrays["env_index"] = idx.astype(np.float64)
+    for k, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (k, a.dtype)
+        np.save(os.path.join(out_dir, f"{k}.npy"), a)
+
+
 def counted_flops(sims, cks, steps, dr, workload, skip=0):
     """Replay the timed window from its checkpoint(s) with the counting kernel variant -- every shard of the batch in turn --:
     the work the timed launches did (the rollout is deterministic), priced with profiles/flop_model.json.  -> dict or None.
@@ -266,15 +336,7 @@ def counted_flops(sims, cks, steps, dr, workload, skip=0):
     c, waves = {}, 0
     for sim, ck in zip(sims, cks):
         try:
-            sim.set_state(ck["q"], ck["qd"])
-            if "solver_lambda" in ck:
-                sim.set_solver_state(ck["solver_lambda"], ck["solver_flags"])
-            sim.set_action_history(0, ck["hist0"]); sim.set_action_history(1, ck["hist1"])
-            if dr:                                    # (restoring parameters would switch a nominal handle to per-env ones)
-                for f, v in ck["params"].items():
-                    sim.set_params(f, v)
-            sim.set_episode_info(ck["steps"], ck["episode"], ck["pose"])
-            sim.step_count = ck["step_count"]
+            rewind(sim, ck, dr)
             if skip:
                 sim.bench_steps(skip)                 # the untimed steps that lay between the checkpoint and the window
             sim.count_work(True)
@@ -336,11 +398,18 @@ def main():
     ap.add_argument("--dump-gathered", default=None,
                     help="with --gather-obs: rank 0 saves the observations / rewards / done flags gathered in the last "
                          "timed step to this .npz (tests compare them with a single handle of all the environments)")
-    ap.add_argument("--no-count", action="store_true", help="skip the counting replay of the timed window")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed path computed in its last step (obs, reward, done, "
+                         "terminal_obs of rank 0's environments) as DIR/<name>.npy, float32 / float64, 64 MB at most")
+    ap.add_argument("--full", action="store_true",
+                    help="also the add-on measurements after the timed window, each with runs of its own: the counting replay "
+                         "(roofline_valu), the open-loop rollout and gym-level lines and the CPU baseline; a plain run "
+                         "measures the headline only")
+    ap.add_argument("--no-count", action="store_true", help="with --full: skip the counting replay of the timed window")
     ap.add_argument("--cpu-envs", type=int, default=2048)
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-gym-level", action="store_true", help="skip the gym-level (HipRuntime.step) and rollout lines")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-gym-level", action="store_true", help="with --full: skip the gym-level (HipRuntime.step) and rollout lines")
     ap.add_argument("--runtime-model", action="store_true",
                     help="perturb the robot constants so that the generic (run-time model) kernels are used")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
@@ -351,7 +420,7 @@ def main():
                     help="cut this rank's batch into that many contiguous shards, one handle and one stream each, advancing "
                          "independently (a shard waits for its own slowest wave only; DESIGN.md 7).  Results per environment "
                          "are those of the single batch, bit for bit.  Pays over long rollouts, once the shards have drifted out of "
-                         "phase (+5 % with 4 shards over 1000 steps, a loss over 20); default 1: one handle, one launch per env-step")
+                         "phase (+5 %% with 4 shards over 1000 steps, a loss over 20); default 1: one handle, one launch per env-step")
     ap.add_argument("--rollout", type=int, default=0, metavar="K",
                     help="a SEPARATE measurement, never the headline: advance in open-loop rollouts of K env-steps per launch "
                          "(os2r_rollout: every wave steps its own environments K times, no device-wide barrier per env-step) instead "
@@ -435,15 +504,17 @@ def main():
             if args.warmup > 0:
                 sims[i].bench_enqueue(args.warmup)
     torch.cuda.synchronize()
-    count = rank == 0 and not args.no_count and not args.gather_obs and args.dtype == "f64" and args.rollout == 0
+    count = args.full and rank == 0 and not args.no_count and not args.gather_obs and args.dtype == "f64" and args.rollout == 0
+    # --dump-outputs recomputes the last timed step from the same checkpoint (the rollout and gather paths have it at hand)
+    replay = bool(args.dump_outputs) and rank == 0 and not args.gather_obs and args.rollout == 0
     for _ in range(3 if use_dist else 0):
         barrier()                                     # communicator set-up and first-use costs of the barrier itself stay outside
-    cks = [s_.checkpoint() for s_ in sims] if count else None   # for the counting replay of the timed window
+    cks = [s_.checkpoint() for s_ in sims] if (count or replay) else None   # for the replays of the timed window
     # A GPU that idles just before the window -- through the checkpoint's small copies, or while the host sits in the
     # opening barrier (150-400 us under RCCL) -- has dropped its clock, and the first launches of a short timed window run
     # up to 6 % slow (measured: 145.6 against 137.9 us per launch over 20 steps behind an RCCL barrier).  So a few more
     # untimed steps are in flight from here until the synchronize that ends the opening bracket.
-    busy_steps = 40
+    busy_steps = BUSY_STEPS
     for i in range(S):
         with on(i):
             # (the first of them through the timed entry point: the first use of the handle's timing events costs the host ~35 us,
@@ -526,6 +597,24 @@ def main():
         import numpy as np
         np.savez(args.dump_gathered, obs=gathered[0].cpu().numpy(), reward=gathered[1].cpu().numpy(), done=gathered[2].cpu().numpy(),
                  steps_run=args.preroll + args.warmup + busy_steps + args.steps)
+    if args.dump_outputs and rank == 0:
+        import numpy as np
+        fdt = np.float64 if args.dtype == "f64" else np.float32
+        if args.rollout > 0:                          # the last launch's outputs, its last env-step
+            outs = {"obs": obs_k[-1], "reward": rew_k[-1], "done": done_k[-1], "terminal_obs": term_k[-1]}
+        elif args.gather_obs:                         # what rank 0 gathered in the last step (the whole job's environments)
+            outs = dict(zip(("obs", "reward", "done"), gathered))
+        else:
+            outs = None
+        if outs is not None:
+            outs = {k: v.cpu().numpy().astype(fdt if k != "done" else np.float32) for k, v in outs.items()}
+        else:
+            ends = []
+            for s_ in sims:
+                q_, qd_ = s_.get_state()
+                ends.append((q_, qd_, s_.step_count))
+            outs = last_step_outputs(sims, streams, cks, ends, WORKLOADS[args.workload][3], busy_steps + args.steps - 1)
+        write_outputs(args.dump_outputs, outs, args.seed)
     if use_dist:
         t = torch.tensor([elapsed, kernel_ms], dtype=torch.float64, device="cuda" if args.backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -591,7 +680,7 @@ def main():
         if spec and "roofline_valu" in out:
             # the specification's straightforward operation count (tests/diag/count_flops.py), for reference only
             out["roofline_valu"]["specification_flops_per_env_step"] = spec["flops_per_env_step"]
-        if world == 1 and S == 1 and args.rollout == 0 and not args.gather_obs and not args.no_gym_level and not getattr(args, "runtime_model", False):
+        if args.full and world == 1 and S == 1 and args.rollout == 0 and not args.gather_obs and not args.no_gym_level and not getattr(args, "runtime_model", False):
             # computed after the timed region, like cpu_baseline: the surface users call, and the open-loop rollout line
             # (add-on measurements: a failure here is recorded, it does not take the headline with it)
             try:
@@ -603,7 +692,7 @@ def main():
                 out["gym_level"] = gym_level(args, cfg, ck_g, value)
             except Exception as e:                    # noqa: BLE001
                 out["gym_level"] = {"error": f"{type(e).__name__}: {e}"}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args, cfg)
         print(json.dumps(out), flush=True)
     for s_ in sims:

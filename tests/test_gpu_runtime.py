@@ -269,11 +269,11 @@ def test_done_mask_and_violation_mirror_come_out_of_the_step_launch(torch_mod):
 
 @pytest.mark.gpu
 def test_bench_prints_the_contract_line():
-    """bench.py: one JSON line with the contract keys, the roofline objects and the CPU baseline (short run)."""
+    """bench.py --full: one JSON line with the contract keys, the roofline objects and the CPU baseline (short run)."""
     import json
     import subprocess
     import sys
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "30", "--warmup", "5",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "30", "--warmup", "5",
                           "--cpu-seconds", "1.0", "--cpu-envs", "256"], stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                          text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -411,6 +411,48 @@ def test_step_can_be_captured_in_a_hip_graph(torch_mod):
     for a, b in zip(eager.get_state(), graphed.get_state()):
         assert torch_mod.equal(a, b)
     eager.close(); graphed.close()
+
+
+@pytest.mark.gpu
+def test_plain_bench_dumps_the_outputs_of_its_last_timed_step(tmp_path):
+    """bench.py without --full measures the headline only (no add-on measurements in the line), and --dump-outputs DIR
+    writes the outputs of the last timed step: what a single handle stepped as often returns, bit for bit."""
+    import argparse
+    import json
+    import subprocess
+    import sys
+    import torch
+    import bench
+    from gym_os2r_amd.sim import HipSim
+    dump = tmp_path / "outputs"
+    preroll, warmup, steps = 20, 3, 12
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+           "--preroll", str(preroll), "--dump-outputs", str(dump)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == steps and d["warmup"] == warmup and d["dtype"] == "f64" and d["unit"] == "env-steps/s"
+    assert d["value"] == pytest.approx(65536 * steps / (d["ms_per_step"] * 1e-3 * steps), rel=1e-6)
+    assert d["roofline"]["bound"] == "hbm"
+    for k in ("roofline_valu", "rollout", "gym_level", "cpu_baseline"):
+        assert k not in d, k
+    got = {k: np.load(dump / f"{k}.npy") for k in ("obs", "reward", "done", "terminal_obs")}
+    assert sorted(p.name for p in dump.iterdir()) == sorted(f"{k}.npy" for k in got)
+    assert all(a.dtype == (np.float32 if k == "done" else np.float64) for k, a in got.items())
+    ns = argparse.Namespace(workload="C4", envs_per_gpu=65536, dtype="f64", seed=42, pgs_iters=None, pgs_exact=None, pgs_normal_iters=None,
+                            pgs_tol=None, runtime_model=False)
+    cfg, _, _ = bench.build_config(ns, 0, 1)
+    sim = HipSim(cfg, device="cuda:0")
+    for _ in range(preroll + warmup + bench.BUSY_STEPS + steps):
+        obs, rew, done, term = sim.step(None)
+    torch.cuda.synchronize()
+    assert np.array_equal(obs.cpu().numpy(), got["obs"])
+    assert np.array_equal(rew.cpu().numpy(), got["reward"])
+    assert np.array_equal(done.cpu().numpy().astype(np.float32), got["done"])
+    assert np.array_equal(term.cpu().numpy(), got["terminal_obs"])
+    sim.close()
 
 
 @pytest.mark.gpu

@@ -18,8 +18,8 @@ PY
 }
 # the stamp build does not travel (.gpurunignore): build it here, on the box's cores
 ( time make -C gym-os2r_amd/csrc STAMPS=1 -j16 ../libos2r_stamps.so > "$OUT/make_stamps.log" 2>&1 ) 2>&1 | grep real
-timeout -k 10 300 python bench.py > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"; show "$OUT/bench_default.json"
-B="timeout -k 10 200 python bench.py --no-cpu-baseline"
+timeout -k 10 300 python bench.py --full > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"; show "$OUT/bench_default.json"
+B="timeout -k 10 200 python bench.py --full --no-cpu-baseline"
 $B --steps 20 --warmup 5 > "$OUT/bench_20_5.json" 2>/dev/null; show "$OUT/bench_20_5.json"
 $B --splits 4 > "$OUT/bench_splits4.json" 2>/dev/null; show "$OUT/bench_splits4.json"
 $B --splits 2 > "$OUT/bench_splits2.json" 2>/dev/null; show "$OUT/bench_splits2.json"

@@ -11,7 +11,7 @@ tail -1 "$OUT/smoke.log"
 for r in 1 2; do
   for v in exact legacy; do
     if [ $v = legacy ]; then EXTRA="--pgs-exact 0 --pgs-iters 20"; else EXTRA=""; fi
-    timeout -k 10 300 python bench.py --no-cpu-baseline $EXTRA > "$OUT/bench_$v.json" 2> "$OUT/bench_$v.err" || { echo "bench $v failed"; tail -5 "$OUT/bench_$v.err"; exit 1; }
+    timeout -k 10 300 python bench.py --full --no-cpu-baseline $EXTRA > "$OUT/bench_$v.json" 2> "$OUT/bench_$v.err" || { echo "bench $v failed"; tail -5 "$OUT/bench_$v.err"; exit 1; }
     python -c "import json;d=json.load(open('$OUT/bench_$v.json'));a=d.get('roofline_valu',{}).get('activity',{});print('$v', round(d['value']/1e6,1), 'M/s', round(d['roofline']['kernel_ms_per_launch']*1e3,2), 'us', {k:round(v,2) for k,v in a.items()})"
   done
 done

@@ -19,7 +19,7 @@ PY
 if [ "${2:-}" != "notest" ]; then
   timeout -k 10 900 python -m pytest tests -m gpu -x -q > "$OUT/pytest.log" 2>&1; echo "pytest rc $?"; tail -4 "$OUT/pytest.log"
 fi
-B="timeout -k 10 200 python bench.py --no-cpu-baseline"
+B="timeout -k 10 200 python bench.py --full --no-cpu-baseline"
 $B > "$OUT/bench_C4.json" 2> "$OUT/bench_C4.err"; show "$OUT/bench_C4.json" | tee -a "$OUT/table.txt"
 $B --steps 20 --warmup 5 --no-count > "$OUT/bench_C4_20_5.json" 2>/dev/null; show "$OUT/bench_C4_20_5.json" | tee -a "$OUT/table.txt"
 for w in C3 V1; do $B --workload $w > "$OUT/bench_$w.json" 2>/dev/null; show "$OUT/bench_$w.json" | tee -a "$OUT/table.txt"; done

@@ -25,8 +25,8 @@ if has test; then
   timeout -k 10 900 python -m pytest tests -m gpu -q > "$OUT/pytest.log" 2>&1; echo "pytest rc $?"; grep -E "^FAILED|passed|failed" "$OUT/pytest.log" | tail -8
 fi
 if has bench; then
-  timeout -k 10 300 python bench.py > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"; show "$OUT/bench_default.json" | tee -a "$OUT/table.txt"
-  B="timeout -k 10 200 python bench.py --no-cpu-baseline"
+  timeout -k 10 300 python bench.py --full > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"; show "$OUT/bench_default.json" | tee -a "$OUT/table.txt"
+  B="timeout -k 10 200 python bench.py --full --no-cpu-baseline"
   run() { n=$1; shift; $B "$@" > "$OUT/bench_$n.json" 2>/dev/null; show "$OUT/bench_$n.json" | tee -a "$OUT/table.txt"; }
   run 20_5 --steps 20 --warmup 5
   run splits4 --splits 4
@@ -49,7 +49,7 @@ if has bench; then
 fi
 if has c2; then
   # C2 (4096 environments = 64 waves on 64 of 1024 SIMDs) is one wave's latency: the same launch time at 4, 16 and 64 times the batch
-  B="timeout -k 10 200 python bench.py --no-cpu-baseline --no-count --workload C2"
+  B="timeout -k 10 200 python bench.py --full --no-cpu-baseline --no-count --workload C2"
   for n in 4096 16384 65536 262144; do
     $B --envs-per-gpu $n --steps 500 > "$OUT/bench_C2_$n.json" 2>/dev/null; show "$OUT/bench_C2_$n.json" | tee -a "$OUT/table_c2.txt"
   done
