@@ -9,7 +9,7 @@ from __future__ import annotations
 import ctypes as C
 from typing import Mapping, Optional
 
-ABI_VERSION = 5
+ABI_VERSION = 6
 MAX_DOF = 5
 MAX_CAND = 192
 MAX_OBS = 12
@@ -29,6 +29,9 @@ RESET_FIXED, RESET_RANDOM = 0, 1
 PARAM_MASS_SCALE, PARAM_DAMPING, PARAM_FRICTION, PARAM_MU, PARAM_GRAVITY = range(5)
 
 DONE_BIT, TRUNCATED_BIT, NONFINITE_BIT = 1, 2, 4
+
+# os2r_rollout_policy flags (include/os2r.h): per-env weights, tanh squash (else clip), sums over the first episode only
+POLICY_PER_ENV, POLICY_TANH, POLICY_FIRST_EPISODE = 1, 2, 4
 
 # solver defaults (config_struct): sweeps only / with the exact finish
 DEFAULT_PGS_ITERS, DEFAULT_PGS_EXACT = 20, 12

@@ -112,6 +112,8 @@ struct SimBase {
   uint32_t* mirror_host = nullptr;      // two words of mapped, coherent host memory (os2r_get_violation_mirror) ...
   uint32_t* mirror_dev = nullptr;       // ... and the address the kernels write them through
   unsigned long long* debug = nullptr;  // diagnostic stamp builds only
+  void* pol_act = nullptr;              // os2r_rollout_policy's launch loop: [N][2] actions, allocated on first use ...
+  uint8_t* pol_open = nullptr;          // ... and [N] "still summing" flags
 };
 
 }  // namespace
@@ -199,7 +201,8 @@ void fill_task(const Os2rConfig& cfg, DevTask<T>& d) {
 
 int validate(const Os2rConfig* c, std::string& why) {
   if (!c) { why = "null config"; return 1; }
-  if (c->abi_version != OS2R_ABI_VERSION) { why = "abi_version mismatch"; return 1; }
+  // (ABI 6 added an entry point, not a field: configs stamped 5 are the same struct)
+  if (c->abi_version != OS2R_ABI_VERSION && c->abi_version != 5) { why = "abi_version mismatch"; return 1; }
   if (c->dtype != OS2R_F32 && c->dtype != OS2R_F64) { why = "dtype must be OS2R_F32 or OS2R_F64"; return 1; }
   if (c->num_envs <= 0) { why = "num_envs must be positive"; return 1; }
   const Os2rModel& m = c->model;
@@ -372,6 +375,53 @@ int dev_alloc(Os2rSim* s, void** p, size_t bytes) {
   return OS2R_OK;
 }
 
+// K env-steps with the linear policy in the loop: one launch of the fused kernel where os2r_rollout has a fused variant;
+// otherwise per env-step the policy kernel (state -> observation -> actions), the step launch with those actions and the
+// accumulation of the step's reward and done flag (same results)
+template <typename T>
+int do_rollout_policy(Os2rSim* s, int K, const void* w, int flags, void* ret, int32_t* len, void* obs, void* reward, uint8_t* done,
+                      void* term, uint16_t* reason, hipStream_t st) {
+  const size_t N = (size_t)s->cfg.num_envs, D = (size_t)s->D;
+  PolicyArgs<T> p;
+  std::memset(&p, 0, sizeof(p));
+  p.w = (const T*)w; p.flags = flags; p.ret = (T*)ret; p.len = len;
+  if (!s->jit && !s->counters) {
+    p.s = make_args<T>(s);
+    p.s.obs = (T*)obs; p.s.reward = (T*)reward; p.s.done = done; p.s.term_obs = (T*)term; p.s.reason = reason;
+    p.s.done_mask = nullptr;   // (neither of the per-step buffers set on the handle is written)
+    p.s.rollout_steps = K;
+    if (Launcher<T>::policy_rollout(s->model_id, s->cfg.contact != 0, s->dr, p, st) == 0) {
+      HIP_TRY(s, hipGetLastError());
+      s->step_count += (unsigned long long)K;
+      return OS2R_OK;
+    }
+  }
+  int rc = OS2R_OK;
+  if (!s->pol_act) {
+    if ((rc = dev_alloc(s, &s->pol_act, 2 * N * s->esz))) return rc;
+    if ((rc = dev_alloc(s, (void**)&s->pol_open, N))) return rc;
+  }
+  p.act = (T*)s->pol_act; p.open = s->pol_open;
+  uint16_t* const reason_keep = s->reason;
+  uint8_t* const mask_keep = s->done_mask;
+  s->done_mask = nullptr;
+  for (int k = 0; k < K && rc == OS2R_OK; ++k) {
+    p.s = make_args<T>(s);
+    if (Launcher<T>::policy(s->nq, p, st) != 0) { s->err = "no policy kernel for this chain length"; rc = OS2R_ERR_INVALID; break; }
+    // the sums need the step's reward and done flag: the handle's scratch outputs stand in for the ones not asked for
+    T* const rew_k = reward ? (T*)reward + (size_t)k * N : (T*)s->b_rew;
+    uint8_t* const done_k = done ? done + (size_t)k * N : s->b_done;
+    s->reason = reason ? reason + (size_t)k * N : nullptr;
+    rc = do_step<T>(s, s->pol_act, obs ? (T*)obs + (size_t)k * N * D : nullptr, rew_k, done_k, term ? (T*)term + (size_t)k * N * D : nullptr, st);
+    if (rc == OS2R_OK && (ret || len))
+      Launcher<T>::accumulate((T*)ret, len, s->pol_open, rew_k, done_k, (long long)N, k, (flags & OS2R_POLICY_FIRST_EPISODE) != 0, st);
+  }
+  s->reason = reason_keep;
+  s->done_mask = mask_keep;
+  if (rc == OS2R_OK) HIP_TRY(s, hipGetLastError());
+  return rc;
+}
+
 void free_all(Os2rSim* s) {
   for (void* p : s->allocs) (void)hipFree(p);
   s->allocs.clear();
@@ -518,6 +568,22 @@ int os2r_rollout(Os2rSim* sim, int nsteps, const void* actions_dev, void* obs_de
   return sim->cfg.dtype == OS2R_F64
              ? do_rollout<double>(sim, nsteps, actions_dev, obs_dev, reward_dev, done_dev, term_obs_dev, reason_dev, (hipStream_t)stream)
              : do_rollout<float>(sim, nsteps, actions_dev, obs_dev, reward_dev, done_dev, term_obs_dev, reason_dev, (hipStream_t)stream);
+}
+
+int os2r_rollout_policy(Os2rSim* sim, int nsteps, const void* weights_dev, int32_t flags, void* return_dev, int32_t* length_dev,
+                        void* obs_dev, void* reward_dev, uint8_t* done_dev, void* term_obs_dev, uint16_t* reason_dev, void* stream) {
+  if (!sim) return OS2R_ERR_INVALID;
+  if (nsteps < 1) { sim->err = "os2r_rollout_policy: nsteps must be >= 1"; return OS2R_ERR_INVALID; }
+  if (!weights_dev) { sim->err = "os2r_rollout_policy: null weights"; return OS2R_ERR_INVALID; }
+  if (flags & ~(OS2R_POLICY_PER_ENV | OS2R_POLICY_TANH | OS2R_POLICY_FIRST_EPISODE)) {
+    sim->err = "os2r_rollout_policy: unknown flag bits";
+    return OS2R_ERR_INVALID;
+  }
+  DeviceGuard guard(sim->cfg.device);
+  hipStream_t st = (hipStream_t)stream;
+  return sim->cfg.dtype == OS2R_F64
+             ? do_rollout_policy<double>(sim, nsteps, weights_dev, flags, return_dev, length_dev, obs_dev, reward_dev, done_dev, term_obs_dev, reason_dev, st)
+             : do_rollout_policy<float>(sim, nsteps, weights_dev, flags, return_dev, length_dev, obs_dev, reward_dev, done_dev, term_obs_dev, reason_dev, st);
 }
 
 int os2r_get_state(Os2rSim* sim, void* q_dev, void* qd_dev, void* stream) {

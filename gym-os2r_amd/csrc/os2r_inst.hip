@@ -112,6 +112,10 @@ template <typename R, int UNIT>
 int step_unit(bool contact, bool dr, const StepArgs<R>& a, hipStream_t s);
 template <typename R, int N_>
 int reset_unit(bool dr, const StepArgs<R>& a, hipStream_t s);
+template <typename R, int UNIT>
+int policy_rollout_unit(bool contact, bool dr, const PolicyArgs<R>& a, hipStream_t s);
+template <typename R, int N_>
+int policy_unit(const PolicyArgs<R>& a, hipStream_t s);
 
 #if OS2R_UNIT < 10
 using MD = StModel<T, OS2R_UNIT>;
@@ -126,7 +130,35 @@ int step_unit<T, OS2R_UNIT>(bool contact, bool dr, const StepArgs<T>& a, hipStre
   return dr ? launch_step<MD, false, true>(a, s) : launch_step<MD, false, false>(a, s);
 }
 
+#if OS2R_UNIT < 10
+// os2r_rollout_policy fused: wherever launch_step has a fused rollout variant (contact, default solver, reference layout)
+template <bool DR>
+static int launch_policy_rollout(const PolicyArgs<T>& p, hipStream_t s) {
+  const StepArgs<T>& a = p.s;
+  if (MD::CMASK == 0u || a.counters || !is_std_solver<T>(a.pgs_iters, a.pgs_normal_iters, a.pgs_exact, MD::NQ)) return 2;
+  const dim3 grid((unsigned)((a.N + kWave - 1) / kWave)), block(kWave);
+  if (layout_is<LayA>(a)) { hipLaunchKernelGGL((policy_rollout_kernel<T, MD, true, DR, LayA>), grid, block, 0, s, p); return 0; }
+#if OS2R_UNIT == 1
+  if (layout_is<LayB>(a)) { hipLaunchKernelGGL((policy_rollout_kernel<T, MD, true, DR, LayB>), grid, block, 0, s, p); return 0; }
+#endif
+  return 2;
+}
+
+template <>
+int policy_rollout_unit<T, OS2R_UNIT>(bool contact, bool dr, const PolicyArgs<T>& p, hipStream_t s) {
+  if (!contact) return 2;
+  return dr ? launch_policy_rollout<true>(p, s) : launch_policy_rollout<false>(p, s);
+}
+#endif
+
 #if OS2R_UNIT >= 10
+template <>
+int policy_unit<T, OS2R_UNIT - 10>(const PolicyArgs<T>& p, hipStream_t s) {
+  const dim3 grid((unsigned)((p.s.N + kWave - 1) / kWave)), block(kWave);
+  hipLaunchKernelGGL((policy_kernel<T, OS2R_UNIT - 10>), grid, block, 0, s, p);
+  return 0;
+}
+
 template <>
 int reset_unit<T, OS2R_UNIT - 10>(bool dr, const StepArgs<T>& a, hipStream_t s) {
   constexpr int NQ = OS2R_UNIT - 10;

@@ -383,6 +383,61 @@ __device__ __forceinline__ void store_obs_tile(T* __restrict__ dst, const T (&ob
 }
 
 // ----------------------------------------------------------------------------------------
+// on-device linear policy (os2r_rollout_policy): a_j = squash(W_j . o + b_j)
+// ----------------------------------------------------------------------------------------
+// The argument of the policy kernels.  It begins with the StepArgs, so that step_body, which re-reads its arguments from the
+// argument segment at offset 0, finds them there; StepArgs itself and every existing kernel stay as they are.
+template <typename T>
+struct PolicyArgs {
+  StepArgs<T> s;
+  const T* __restrict__ w;   // [2][D+1] shared, or [2][D+1][N] (OS2R_POLICY_PER_ENV); row j: W_j0 .. W_j,D-1, b_j
+  int flags;                 // OS2R_POLICY_*
+  T* __restrict__ ret;       // [N] or null: rewards summed in step order
+  int32_t* __restrict__ len; // [N] or null: env-steps summed
+  T* __restrict__ act;       // launch loop only: [N][2] actions the policy kernel hands to the step launch
+  uint8_t* __restrict__ open;// launch loop only: [N] 1 while the environment's returns are still summed
+};
+
+// The one policy function of both paths (fused rollout, launch loop).  Evaluation order is part of the contract
+// (include/os2r.h): z_j = (((b_j + W_j0*o_0) + W_j1*o_1) + ...), each product rounded on its own.  Shared weights are
+// wave-uniform (scalar loads); per-env ones are [2(D+1)][N] and load coalesced.
+template <typename T>
+__device__ __forceinline__ void policy_action(const T* __restrict__ w, int flags, int D, long long N, long long e,
+                                              const T (&obs)[OS2R_MAX_OBS], T& ax, T& ay) {
+#pragma clang fp contract(off)
+  const int R = D + 1;
+  T z[2];
+  if (flags & OS2R_POLICY_PER_ENV) {
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      T acc = w[(long long)(j * R + D) * N + e];
+#pragma unroll
+      for (int d = 0; d < OS2R_MAX_OBS; ++d)
+        if (d < D) acc = acc + w[(long long)(j * R + d) * N + e] * obs[d];
+      z[j] = acc;
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      T acc = w[j * R + D];
+#pragma unroll
+      for (int d = 0; d < OS2R_MAX_OBS; ++d)
+        if (d < D) acc = acc + w[j * R + d] * obs[d];
+      z[j] = acc;
+    }
+  }
+  if (flags & OS2R_POLICY_TANH) {
+    z[0] = tanh_t(z[0]);
+    z[1] = tanh_t(z[1]);
+  } else {
+#pragma unroll
+    for (int j = 0; j < 2; ++j) z[j] = z[j] < T(-1) ? T(-1) : (z[j] > T(1) ? T(1) : z[j]);
+  }
+  ax = z[0];
+  ay = z[1];
+}
+
+// ----------------------------------------------------------------------------------------
 // env-step kernel: GazeboRuntime.step (runtimes/gazebo_runtime.py:65-97) for every env
 // ----------------------------------------------------------------------------------------
 // LDS of one wave: during the physics iterations it holds the Minv*J^T rows of the contact
@@ -419,9 +474,13 @@ constexpr int std_solver(bool std_sweeps, bool is_f64, bool std_exact) {
 // the slowest -- with the state in registers from the first step to the last; step k writes its observation, reward,
 // done flag (terminal observation, done reason) at offset k of the [K][N]... output arrays and takes its actions from
 // slice k of the [K][N][2] input (or draws them with the step counter + k).  The arithmetic of a step is the same code.
+// POLICY (with ROLLOUT; os2r_rollout_policy): the kernel's argument is a PolicyArgs; each step's action is the linear policy of
+// the observation the environment's previous step returned -- recomputed from the state the step loads anyway -- and the
+// owning lane adds the step's reward and count to the environment's return and length.
 template <typename T, typename MD, bool CONTACT, bool DR, bool STD_SWEEPS = false, typename LAY = RtLayout, bool COUNT = false,
-          int SOLVER = std_solver(STD_SWEEPS, sizeof(T) == 8, StdSolver<T>::kExact), bool ROLLOUT = false>
+          int SOLVER = std_solver(STD_SWEEPS, sizeof(T) == 8, StdSolver<T>::kExact), bool ROLLOUT = false, bool POLICY = false>
 __device__ __forceinline__ void step_body(const StepArgs<T>& A) {
+  static_assert(!POLICY || ROLLOUT, "the policy runs in the fused rollout");
   constexpr int NQ = MD::NQ;
   // run-time models scan a wave-shared LDS copy of the candidate table; the compiled-in ones read the
   // (wave-uniform) coordinates through scalar loads, straight into the operands of the scan
@@ -461,6 +520,7 @@ __device__ __forceinline__ void step_body(const StepArgs<T>& A) {
   T sn[NQ], cs[NQ];   // sin/cos of the joint angles, carried from one physics iteration to the next
   WorkCounts wc;
   const int nsteps = ROLLOUT ? A.rollout_steps : 1;
+  [[maybe_unused]] bool summing = true;   // POLICY: this environment's return and length still take its steps
   for (int k = 0; k < nsteps; ++k) {
     const long long ko = ROLLOUT ? (long long)k * A.N : 0ll;   // this step's slice of the output arrays
     // (a rollout passes the state from one env-step to the next through memory like separate launches do -- its own
@@ -498,7 +558,17 @@ __device__ __forceinline__ void step_body(const StepArgs<T>& A) {
     const unsigned long long step_count = A.step_count + (unsigned long long)k;
     // action: caller-provided or drawn from the counter RNG (stream 1, counter = step count)
     T ax, ay;
-    if (A.actions) {
+    if constexpr (POLICY) {
+      // the observation the previous step (or reset) returned: observe() of the stored state, as reset_kernel makes it
+      // (the weights are loaded here and are dead before the physics iterations)
+      const PolicyArgs<T>* pa = (const PolicyArgs<T>*)__builtin_amdgcn_kernarg_segment_ptr();
+      const T h2x = A.hist[2 * A.N + e], h2y = A.hist[3 * A.N + e];
+      T o[OS2R_MAX_OBS];
+      bool dn0;
+      unsigned why0;
+      observe<T, NQ, LAY>(ts, q, qd, h2x, h2y, o, dn0, why0);
+      policy_action<T>(pa->w, pa->flags, D, A.N, e, o, ax, ay);
+    } else if (A.actions) {
       ax = A.actions[2 * (ko + e)];
       ay = A.actions[2 * (ko + e) + 1];
       // (the lanes behind the last environment of a tail wave shadow it and must not count its action again)
@@ -625,6 +695,16 @@ __device__ __forceinline__ void step_body(const StepArgs<T>& A) {
       if (Ae.done) Ae.done[ko + ep] = flag;
       if (Ae.reason) Ae.reason[ko + ep] = (uint16_t)why;
       if (Ae.done_mask) Ae.done_mask[ko + ep] = flag != 0 ? (uint8_t)1 : (uint8_t)0;
+      if constexpr (POLICY) {
+        // return and length: a read-modify-write by the owning lane (the same lines as the state), started afresh at k = 0
+        const PolicyArgs<T>* pe = (const PolicyArgs<T>*)__builtin_amdgcn_kernarg_segment_ptr();
+        asm volatile("" : "+s"(pe));
+        if (summing) {
+          if (pe->ret) pe->ret[ep] = (k == 0 ? T(0) : pe->ret[ep]) + rew;
+          if (pe->len) pe->len[ep] = (k == 0 ? 0 : pe->len[ep]) + 1;
+        }
+        if ((pe->flags & OS2R_POLICY_FIRST_EPISODE) && flag != 0) summing = false;
+      }
     }
     if (valid) {
 #pragma unroll
@@ -684,6 +764,57 @@ template <typename T, typename MD, bool CONTACT, bool DR, bool STD_SWEEPS, typen
           int SOLVER = std_solver(STD_SWEEPS, sizeof(T) == 8, StdSolver<T>::kExact), bool ROLLOUT = false>
 __global__ OS2R_STEP_KERNEL_ATTRS(T) void step_kernel(const StepArgs<T> A) {
   step_body<T, MD, CONTACT, DR, STD_SWEEPS, LAY, COUNT, SOLVER, ROLLOUT>(A);
+}
+
+// os2r_rollout_policy, fused: the rollout variant of step_kernel (default solver compiled in) with the policy in the loop.  Its
+// one argument begins with the StepArgs (step_body reads the argument segment at offset 0).
+template <typename T, typename MD, bool CONTACT, bool DR, typename LAY>
+__global__ OS2R_STEP_KERNEL_ATTRS(T) void policy_rollout_kernel(const PolicyArgs<T> P) {
+  step_body<T, MD, CONTACT, DR, true, LAY, false, std_solver(true, sizeof(T) == 8, StdSolver<T>::kExact), true, true>(P.s);
+}
+
+// os2r_rollout_policy, launch loop (the configurations without a fused variant): per env-step this kernel turns the stored state
+// into the observation and the policy's actions ([N][2], P.act), the step launch takes them, policy_accumulate_kernel sums.
+template <typename T, int NQ>
+__global__ __launch_bounds__(kWave) void policy_kernel(const PolicyArgs<T> P) {
+  const StepArgs<T>& A = P.s;
+  const int lane = threadIdx.x;
+  const long long e0 = (long long)blockIdx.x * kWave;
+  const bool valid = e0 + lane < A.N;
+  const long long e = valid ? e0 + lane : A.N - 1;
+  const TaskPtr<T> ts = as_const(A.task);
+  T q[NQ], qd[NQ];
+#pragma unroll
+  for (int i = 0; i < NQ; ++i) {
+    q[i] = A.q[i * A.N + e];
+    qd[i] = A.qd[i * A.N + e];
+  }
+  const T h2x = A.hist[2 * A.N + e], h2y = A.hist[3 * A.N + e];
+  T obs[OS2R_MAX_OBS];
+  bool dn;
+  unsigned why;
+  observe<T, NQ>(ts, q, qd, h2x, h2y, obs, dn, why);
+  T ax, ay;
+  policy_action<T>(P.w, P.flags, ts->obs_dim, A.N, e, obs, ax, ay);
+  if (valid) {
+    P.act[2 * e] = ax;
+    P.act[2 * e + 1] = ay;
+  }
+}
+
+// step k's reward and done flag into the return and length (launch loop); the same sums as the fused epilogue
+template <typename T>
+__global__ void policy_accumulate_kernel(T* __restrict__ ret, int32_t* __restrict__ len, uint8_t* __restrict__ open,
+                                         const T* __restrict__ rew, const uint8_t* __restrict__ done, long long N, int k,
+                                         int first_episode) {
+  const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= N) return;
+  const bool summing = k == 0 || open[e] != 0;
+  if (summing) {
+    if (ret) ret[e] = (k == 0 ? T(0) : ret[e]) + rew[e];
+    if (len) len[e] = (k == 0 ? 0 : len[e]) + 1;
+  }
+  open[e] = (summing && !(first_episode && done[e] != 0)) ? (uint8_t)1 : (uint8_t)0;
 }
 
 // ----------------------------------------------------------------------------------------
@@ -759,6 +890,11 @@ struct Launcher {
   static int reset(int nq, bool dr, const StepArgs<T>& args, hipStream_t stream);
   static void gravity(T* g, long long N, long long off, unsigned long long seed, double mean, double std_, hipStream_t s);
   static void fill(T* dst, long long n, T value, hipStream_t s);
+  // os2r_rollout_policy: the fused kernel (2: none for this configuration), the policy kernel of the launch loop, the sums
+  static int policy_rollout(int model_id, bool contact, bool dr, const PolicyArgs<T>& args, hipStream_t stream);
+  static int policy(int nq, const PolicyArgs<T>& args, hipStream_t stream);
+  static void accumulate(T* ret, int32_t* len, uint8_t* open, const T* rew, const uint8_t* done, long long N, int k,
+                         int first_episode, hipStream_t s);
 };
 
 }  // namespace os2r

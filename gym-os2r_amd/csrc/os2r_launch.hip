@@ -7,13 +7,21 @@ template <typename R, int UNIT>
 int step_unit(bool contact, bool dr, const StepArgs<R>& a, hipStream_t s);
 template <typename R, int N_>
 int reset_unit(bool dr, const StepArgs<R>& a, hipStream_t s);
+template <typename R, int UNIT>
+int policy_rollout_unit(bool contact, bool dr, const PolicyArgs<R>& a, hipStream_t s);
+template <typename R, int N_>
+int policy_unit(const PolicyArgs<R>& a, hipStream_t s);
 
 #define OS2R_DECL_STEP(R, U) template <> int step_unit<R, U>(bool, bool, const StepArgs<R>&, hipStream_t);
 #define OS2R_DECL_RESET(R, N_) template <> int reset_unit<R, N_>(bool, const StepArgs<R>&, hipStream_t);
+#define OS2R_DECL_PROLL(R, U) template <> int policy_rollout_unit<R, U>(bool, bool, const PolicyArgs<R>&, hipStream_t);
+#define OS2R_DECL_POLICY(R, N_) template <> int policy_unit<R, N_>(const PolicyArgs<R>&, hipStream_t);
 #define OS2R_DECL(R)                                                                              \
   OS2R_DECL_STEP(R, 0) OS2R_DECL_STEP(R, 1) OS2R_DECL_STEP(R, 2) OS2R_DECL_STEP(R, 3)               \
   OS2R_DECL_STEP(R, 12) OS2R_DECL_STEP(R, 13) OS2R_DECL_STEP(R, 14) OS2R_DECL_STEP(R, 15)           \
-  OS2R_DECL_RESET(R, 2) OS2R_DECL_RESET(R, 3) OS2R_DECL_RESET(R, 4) OS2R_DECL_RESET(R, 5)
+  OS2R_DECL_RESET(R, 2) OS2R_DECL_RESET(R, 3) OS2R_DECL_RESET(R, 4) OS2R_DECL_RESET(R, 5)           \
+  OS2R_DECL_PROLL(R, 0) OS2R_DECL_PROLL(R, 1) OS2R_DECL_PROLL(R, 2) OS2R_DECL_PROLL(R, 3)           \
+  OS2R_DECL_POLICY(R, 2) OS2R_DECL_POLICY(R, 3) OS2R_DECL_POLICY(R, 4) OS2R_DECL_POLICY(R, 5)
 OS2R_DECL(float)
 OS2R_DECL(double)
 
@@ -43,6 +51,32 @@ int Launcher<T>::reset(int nq, bool dr, const StepArgs<T>& a, hipStream_t s) {
     case 5: return reset_unit<T, 5>(dr, a, s);
     default: return 1;
   }
+}
+template <typename T>
+int Launcher<T>::policy_rollout(int model_id, bool contact, bool dr, const PolicyArgs<T>& a, hipStream_t s) {
+  switch (model_id) {
+    case 0: return policy_rollout_unit<T, 0>(contact, dr, a, s);
+    case 1: return policy_rollout_unit<T, 1>(contact, dr, a, s);
+    case 2: return policy_rollout_unit<T, 2>(contact, dr, a, s);
+    case 3: return policy_rollout_unit<T, 3>(contact, dr, a, s);
+    default: return 2;   // run-time models: no fused variant
+  }
+}
+template <typename T>
+int Launcher<T>::policy(int nq, const PolicyArgs<T>& a, hipStream_t s) {
+  switch (nq) {
+    case 2: return policy_unit<T, 2>(a, s);
+    case 3: return policy_unit<T, 3>(a, s);
+    case 4: return policy_unit<T, 4>(a, s);
+    case 5: return policy_unit<T, 5>(a, s);
+    default: return 1;
+  }
+}
+template <typename T>
+void Launcher<T>::accumulate(T* ret, int32_t* len, uint8_t* open, const T* rew, const uint8_t* done, long long N, int k,
+                             int first_episode, hipStream_t s) {
+  hipLaunchKernelGGL((policy_accumulate_kernel<T>), dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, ret, len, open, rew, done, N,
+                     k, first_episode);
 }
 template <typename T>
 void Launcher<T>::gravity(T* g, long long N, long long off, unsigned long long seed, double mean, double std_,

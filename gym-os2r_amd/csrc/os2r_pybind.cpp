@@ -32,6 +32,10 @@ PYBIND11_MODULE(_os2r_py, m) {
     return os2r_step(H(h), P(act), P(obs), P(rew), (uint8_t*)P(done), P(term), P(st)); }, nogil);
   m.def("rollout", [](addr h, int n, addr act, addr obs, addr rew, addr done, addr term, addr why, addr st) {
     return os2r_rollout(H(h), n, P(act), P(obs), P(rew), (uint8_t*)P(done), P(term), (uint16_t*)P(why), P(st)); }, nogil);
+  m.def("rollout_policy", [](addr h, int n, addr w, int flags, addr ret, addr len, addr obs, addr rew, addr done, addr term, addr why,
+                             addr st) {
+    return os2r_rollout_policy(H(h), n, P(w), flags, P(ret), (int32_t*)P(len), P(obs), P(rew), (uint8_t*)P(done), P(term),
+                               (uint16_t*)P(why), P(st)); }, nogil);
   m.def("get_solver_state", [](addr h, addr l, addr f, addr st) { return os2r_get_solver_state(H(h), P(l), (uint32_t*)P(f), P(st)); }, nogil);
   m.def("set_solver_state", [](addr h, addr l, addr f, addr st) { return os2r_set_solver_state(H(h), P(l), (const uint32_t*)P(f), P(st)); }, nogil);
   m.def("get_state", [](addr h, addr q, addr qd, addr st) { return os2r_get_state(H(h), P(q), P(qd), P(st)); }, nogil);

@@ -64,6 +64,10 @@ class _PybindLib:
         return self.m.rollout(self._a(h), int(n), self._a(act), self._a(obs), self._a(rew), self._a(done), self._a(term),
                               self._a(reason), self._a(st))
 
+    def os2r_rollout_policy(self, h, n, w, flags, ret, length, obs, rew, done, term, reason, st):
+        return self.m.rollout_policy(self._a(h), int(n), self._a(w), int(flags), self._a(ret), self._a(length), self._a(obs),
+                                     self._a(rew), self._a(done), self._a(term), self._a(reason), self._a(st))
+
     def os2r_get_action_history(self, h, w, o, st):
         return self.m.get_action_history(self._a(h), int(w), self._a(o), self._a(st))
 
@@ -252,6 +256,43 @@ class HipSim:
         self._out(reasons, (K, self.N), torch.int16, "reasons")
         self._check(self._lib.os2r_rollout(self._h, int(nsteps), _ptr(actions), _ptr(obs), _ptr(rew), _ptr(done), _ptr(term),
                                            _ptr(reasons), self._stream()), "os2r_rollout")
+
+    def rollout_policy(self, nsteps: int, weights, *, tanh: bool = False, first_episode: bool = False, want_outputs: bool = False,
+                       want_terminal: bool = False, want_reasons: bool = False):
+        """`nsteps` env-steps with the linear policy a = squash(W.o + b) in the loop, evaluated on the device on every environment's
+        own observation (include/os2r.h: os2r_rollout_policy; one launch where os2r_rollout has a fused kernel).
+        weights: [2, D+1] shared by all environments or [N, 2, D+1] one set per environment; row j (0 hip, 1 knee) holds
+        W_j0 .. W_j,D-1, b_j.  squash: clip to [-1, 1], or tanh.  first_episode: the sums stop after an environment's first
+        done flag in the window.  -> (returns [N], lengths [N] int32, outputs): outputs is the rollout() tuple
+        (obs, reward, done, terminal_obs, reasons) when want_outputs, else None (nothing per step is written then)."""
+        K = int(nsteps)
+        if K < 1:
+            raise ValueError("rollout_policy: nsteps must be >= 1")
+        R = self.D + 1
+        if not isinstance(weights, torch.Tensor):
+            weights = torch.as_tensor(weights)
+        shape = tuple(weights.shape)
+        flags = (abi.POLICY_TANH if tanh else 0) | (abi.POLICY_FIRST_EPISODE if first_episode else 0)
+        if shape == (2, R):
+            w = weights
+        elif shape == (self.N, 2, R):
+            w = weights.permute(1, 2, 0)                  # the kernel's layout: [2][D+1][N], env index fastest
+            flags |= abi.POLICY_PER_ENV
+        else:
+            raise ValueError(f"rollout_policy: weights must be [2, {R}] or [{self.N}, 2, {R}], got {shape}")
+        if weights.dtype != self.dtype or weights.device != self.device:
+            raise ValueError(f"rollout_policy: weights must be {self.dtype} on {self.device}, got {weights.dtype} on {weights.device}")
+        w = w.contiguous()
+        ret, length = self._new(self.N), self._new(self.N, dtype=torch.int32)
+        obs = rew = done = term = why = None
+        if want_outputs:
+            obs, rew = self._new(K, self.N, self.D), self._new(K, self.N)
+            done = self._new(K, self.N, dtype=torch.uint8)
+            term = self._new(K, self.N, self.D) if want_terminal else None
+            why = self._new(K, self.N, dtype=torch.int16) if want_reasons else None
+        self._check(self._lib.os2r_rollout_policy(self._h, K, _ptr(w), flags, _ptr(ret), _ptr(length), _ptr(obs), _ptr(rew),
+                                                  _ptr(done), _ptr(term), _ptr(why), self._stream()), "os2r_rollout_policy")
+        return ret, length, ((obs, rew, done, term, why) if want_outputs else None)
 
     def reset(self, mask: Optional[torch.Tensor] = None):
         m = None if mask is None else self._in(mask, (self.N,), torch.uint8)

@@ -39,7 +39,7 @@ extern "C" {
 #define OS2R_API
 #endif
 
-#define OS2R_ABI_VERSION 5
+#define OS2R_ABI_VERSION 6   /* os2r_create also takes configs stamped 5 (Os2rConfig did not change in 6) */
 
 #define OS2R_MAX_DOF 5      /* yaw, pitch, boom_connector, hip, knee                       */
 #define OS2R_MAX_CAND 192   /* ground-contact candidate points of one model                */
@@ -155,7 +155,7 @@ typedef struct Os2rTaskSpec {
 } Os2rTaskSpec;
 
 typedef struct Os2rConfig {
-  int32_t abi_version;     /* must be OS2R_ABI_VERSION                                      */
+  int32_t abi_version;     /* OS2R_ABI_VERSION (5 is accepted too: same struct)               */
   int32_t dtype;           /* OS2R_F32 / OS2R_F64                                            */
   int64_t num_envs;        /* environments owned by this handle (this rank's shard)          */
   int64_t env_offset;      /* global index of local env 0 (multi-GPU sharding; RNG key)      */
@@ -233,13 +233,42 @@ OS2R_API int os2r_step(Os2rSim* sim, const void* actions_dev, void* obs_dev, voi
  * with ground contact, the default solver settings and a reference task layout) the whole rollout is ONE launch in which
  * every wave advances its own 64 environments step after step, state in registers; otherwise the library makes the
  * `nsteps` launches itself.  For open-loop action sequences and random rollouts (the reference's workers advance
- * independently of each other: gym_os2r/common/vec_env/subproc_vec_env.py:15-21); a policy in the loop needs os2r_step.
+ * independently of each other: gym_os2r/common/vec_env/subproc_vec_env.py:15-21); a linear policy in the loop runs the same way
+ * through os2r_rollout_policy (below).
  *   actions_dev  [nsteps][num_envs][2] or NULL (on-device U(-1,1) actions, step counter as in os2r_step)
  *   obs_dev      [nsteps][num_envs][obs_dim], reward_dev [nsteps][num_envs], done_dev [nsteps][num_envs] uint8,
  *   term_obs_dev [nsteps][num_envs][obs_dim] (nullable), reason_dev [nsteps][num_envs] uint16 (nullable; the done
  *                reasons of os2r_set_done_reasons per step -- the buffer set there is not written by a rollout)  */
 OS2R_API int os2r_rollout(Os2rSim* sim, int nsteps, const void* actions_dev, void* obs_dev, void* reward_dev,
                           uint8_t* done_dev, void* term_obs_dev, uint16_t* reason_dev, void* stream);
+
+/* Closed-loop rollouts with an on-device linear policy (ABI 6): `nsteps` env-steps of every environment in which the action of
+ * each env-step is a = squash(W.o + b), evaluated on the environment's own observation o -- the one its previous env-step (or
+ * reset) returned, post-reset after an auto-reset; it is recomputed from the stored state at the top of each env-step.  The
+ * handle advances exactly as `nsteps` calls of os2r_step(actions = policy(o)) would advance it, bit for bit: state, contact
+ * solver state, action history, episode counters, resets and TimeLimit truncations, step counter += nsteps.  Policy actions lie
+ * in [-1, 1]: they are never counted as violations.  The handle's done-reason and done-mask buffers are not written.  Fused
+ * into one launch where os2r_rollout has a fused variant; otherwise the library runs a policy launch, the step launch and an
+ * accumulation launch per env-step (same results).
+ *   weights_dev  handle's dtype; row j (0 = hip, 1 = knee) holds W_j0 ... W_j,D-1, b_j (D = obs_dim):
+ *                [2][D+1] shared by all environments, or [2][D+1][num_envs] (env index fastest) with OS2R_POLICY_PER_ENV
+ *   flags        OS2R_POLICY_* bits
+ *                z_j = (((b_j + W_j0*o_0) + W_j1*o_1) + ...), every product rounded on its own (no fused multiply-add): a plain
+ *                loop of tensor operations reproduces the action bit for bit; a_j = min(max(z_j, -1), 1), or tanh(z_j)
+ *   return_dev   [num_envs] handle's dtype (nullable), overwritten: the rewards summed in step order, (r_0 + r_1) + ...
+ *   length_dev   [num_envs] int32 (nullable): the number of env-steps summed.  Without OS2R_POLICY_FIRST_EPISODE both cover
+ *                all `nsteps`; with it the sums stop after the first env-step whose done byte is non-zero (that step included)
+ *                -- the environment itself keeps stepping and resetting
+ *   obs_dev, reward_dev, done_dev, term_obs_dev, reason_dev: the [nsteps][num_envs]... outputs of os2r_rollout, every one
+ *                nullable here: a pure evaluation writes nothing per step but the state
+ * Errors: OS2R_ERR_INVALID for nsteps < 1, a null weights_dev or an unknown flag bit (os2r_last_error says which).          */
+#define OS2R_POLICY_PER_ENV 1       /* weights [2][D+1][N], env index fastest; else one set [2][D+1] for all envs */
+#define OS2R_POLICY_TANH 2          /* a_j = tanh(z_j); else a_j = min(max(z_j, -1), 1)                      */
+#define OS2R_POLICY_FIRST_EPISODE 4 /* return/length stop after the env's first done flag in the window      */
+OS2R_API int os2r_rollout_policy(Os2rSim* sim, int nsteps, const void* weights_dev, int32_t flags,
+                                 void* return_dev, int32_t* length_dev,
+                                 void* obs_dev, void* reward_dev, uint8_t* done_dev, void* term_obs_dev,
+                                 uint16_t* reason_dev, void* stream);
 
 /* Model-specialised kernels.  A robot that is not one of the four compiled-in reference variants
  * runs on generic kernels that read its constants through scalar loads (about half the speed).
