@@ -6,6 +6,8 @@
 // CPU; a missing GPU is an error (OS2R_ERR_NO_DEVICE), never a fallback.
 #include <hip/hip_runtime.h>
 
+#include <cfloat>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <new>
@@ -164,6 +166,30 @@ void fill_model(const Os2rModel& m_in, bool contact, DevModel<T>& d) {
   }
 }
 
+// The done test of observe() is `x < done_lo || x > done_hi` on the pre-map value x.  done_lo / done_hi are exact
+// f64 pre-images of the reference's test; in f32 they must decide what they decide in f64 for every float x:
+// a bound rounded to nearest may land on the far side of a float the reference flags (the torque slots:
+// -/+0.9999999999999998 -> -/+1.0f, and an action of exactly -/+1 no longer ends the episode).  So a bound rounds
+// inward: done_lo up to the smallest float >= it, done_hi down to the largest float <= it.  Periodic slots are the
+// exception: the f32 wrap_pi returns -pi_f (just below -pi) for x = +/-pi_f, inputs the reference keeps, so their
+// bounds round outward instead, to keep the whole range of the f32 wrap [-pi_f, pi_f] inside.
+inline float float_at_or_above(double v) {
+  float f = (float)v;
+  if ((double)f < v) f = std::nextafter(f, FLT_MAX);
+  return f;
+}
+inline float float_at_or_below(double v) {
+  float f = (float)v;
+  if ((double)f > v) f = std::nextafter(f, -FLT_MAX);
+  return f;
+}
+inline void done_bounds(int kind, double lo, double hi, double& dlo, double& dhi) { dlo = lo; dhi = hi; }
+inline void done_bounds(int kind, double lo, double hi, float& dlo, float& dhi) {
+  const bool periodic = kind == OS2R_OBS_POS_PERIODIC_NORM || kind == OS2R_OBS_POS_PERIODIC_RAW;
+  dlo = periodic ? float_at_or_below(lo) : float_at_or_above(lo);
+  dhi = periodic ? float_at_or_above(hi) : float_at_or_below(hi);
+}
+
 template <typename T>
 void fill_task(const Os2rConfig& cfg, DevTask<T>& d) {
   const Os2rTaskSpec& t = cfg.task;
@@ -174,8 +200,7 @@ void fill_task(const Os2rConfig& cfg, DevTask<T>& d) {
     d.obs_src[i] = t.obs_src[i];
     d.obs_low[i] = (T)t.obs_low[i];
     d.obs_high[i] = (T)t.obs_high[i];
-    d.done_lo[i] = (T)t.done_lo[i];
-    d.done_hi[i] = (T)t.done_hi[i];
+    done_bounds(t.obs_kind[i], t.done_lo[i], t.done_hi[i], d.done_lo[i], d.done_hi[i]);
   }
   d.reward_id = t.reward_id; d.normalized = t.normalized;
   d.idx_pitch_pos = t.idx_pitch_pos; d.idx_yaw_vel = t.idx_yaw_vel;

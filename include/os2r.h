@@ -156,7 +156,11 @@ typedef struct Os2rTaskSpec {
 
 typedef struct Os2rConfig {
   int32_t abi_version;     /* OS2R_ABI_VERSION (5 is accepted too: same struct)               */
-  int32_t dtype;           /* OS2R_F32 / OS2R_F64                                            */
+  int32_t dtype;           /* OS2R_F32 / OS2R_F64.  F32: done and every done-reason bit equal  */
+                           /*   what the reference decides in f64 on the f32 state (the done   */
+                           /*   bounds are rounded inward to float); observations and rewards  */
+                           /*   are only close: a normalised observation may read -/+1.0f      */
+                           /*   while the environment is inside the reset space.               */
   int64_t num_envs;        /* environments owned by this handle (this rank's shard)          */
   int64_t env_offset;      /* global index of local env 0 (multi-GPU sharding; RNG key)      */
   uint64_t seed;

@@ -46,3 +46,47 @@ def perturbed_model(mode, rng):
     m["friction"] = [0.004 * rng.uniform(0.5, 1.5) for _ in range(nq)]
     m["mu"] = [rng.uniform(0.3, 1.0) for _ in range(nq)]
     return m
+
+
+def mixed_axis_chain(tmp_path):
+    """A hand-made 3-dof chain with joint axes z, y, x and contact candidates on every body, and a raw-observation task for
+    it: -> (model dict, task spec dict)."""
+    from gym_os2r_amd.model_compiler import compile_urdf
+    urdf = tmp_path / "arm.urdf"
+    urdf.write_text("""<robot name="arm">
+      <link name="world"/>
+      <link name="l0"><inertial><origin xyz="0.05 0 0.1" rpy="0.1 0 0"/><mass value="1.5"/>
+        <inertia ixx="0.02" ixy="0.001" ixz="0" iyy="0.03" iyz="0.002" izz="0.01"/></inertial></link>
+      <link name="l1"><inertial><origin xyz="0 0.1 -0.15" rpy="0 0.2 0"/><mass value="0.7"/>
+        <inertia ixx="0.004" ixy="0" ixz="0.0005" iyy="0.005" iyz="0" izz="0.002"/></inertial></link>
+      <link name="l2"><inertial><origin xyz="0.02 0 -0.1" rpy="0 0 0"/><mass value="0.3"/>
+        <inertia ixx="0.001" ixy="0" ixz="0" iyy="0.0012" iyz="0" izz="0.0004"/></inertial></link>
+      <joint name="hip_joint" type="continuous"><origin xyz="0 0 0.35" rpy="0.3 0 0.2"/><parent link="world"/><child link="l0"/>
+        <axis xyz="0 0 1"/><dynamics damping="0.02" friction="0.01"/></joint>
+      <joint name="knee_joint" type="continuous"><origin xyz="0.1 0 0" rpy="0 0.4 0"/><parent link="l0"/><child link="l1"/>
+        <axis xyz="0 1 0"/><dynamics damping="0.01" friction="0.02"/></joint>
+      <joint name="ankle" type="continuous"><origin xyz="0 0 -0.3" rpy="1.57 0 0"/><parent link="l1"/><child link="l2"/>
+        <axis xyz="1 0 0"/><dynamics damping="0.005" friction="0.0"/></joint>
+    </robot>""")
+    m = compile_urdf(str(urdf), actuated=("hip_joint", "knee_joint"), with_meshes=False)
+    assert m["axis"] == [2, 1, 0]
+    # contact candidates by hand: a few points on every body (body-frame coordinates)
+    pts = {0: [[0.1, 0.0, -0.05], [0.0, 0.05, -0.08], [0.12, 0.02, 0.0]],
+           1: [[0.0, 0.0, -0.3], [0.03, 0.0, -0.28], [-0.03, 0.01, -0.29], [0.0, 0.02, -0.15]],
+           2: [[0.0, 0.0, -0.2], [0.02, 0.0, -0.2], [0.0, 0.03, -0.18]]}
+    m["cand_body"], m["cand_p"] = [], []
+    for b in sorted(pts):
+        for p in pts[b]:
+            m["cand_body"].append(b); m["cand_p"].append(p)
+    m["ncand"] = len(m["cand_body"])
+    inf = float("inf")
+    spec = {"obs_dim": 6, "obs_kind": [abi.OBS_POS_RAW] * 3 + [abi.OBS_VEL_RAW] * 3, "obs_src": [0, 1, 2, 0, 1, 2],
+            "obs_low": [-inf] * 6, "obs_high": [inf] * 6, "done_lo": [-inf] * 6, "done_hi": [inf] * 6,
+            "reward_id": abi.REWARD_STRAIGHT_V1, "normalized": 0, "idx_pitch_pos": -1, "idx_yaw_vel": -1,
+            "idx_hip_pos": 0, "idx_knee_pos": 1, "max_episode_steps": 0, "reset_mode": abi.RESET_FIXED,
+            "reset_pose_id": [0], "reset_laying": [0], "reset_pitch": [0.0], "reset_hip": [0.3], "reset_knee": [-0.4],
+            "reset_simple": 0, "leg_def": [200, 190, 80, 2100, 0, 25], "dof_yaw": -1, "dof_pitch": -1, "dof_bc": -1,
+            "dof_hip": 0, "dof_knee": 1, "randomize_params": 0, "dr_mass_lo": 1, "dr_mass_hi": 1, "dr_friction_lo": 0,
+            "dr_friction_hi": 0, "dr_damping_lo": 1, "dr_damping_hi": 1, "dr_mu_base": 1, "dr_mu_lo": 1, "dr_mu_hi": 1,
+            "dr_gravity_mean": -9.8, "dr_gravity_std": 0.0}
+    return m, spec

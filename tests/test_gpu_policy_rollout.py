@@ -14,7 +14,9 @@ from gym_os2r_amd import abi
 pytestmark = pytest.mark.gpu
 
 # the configurations of test_rollout_equals_step_by_step: fused where os2r_rollout is fused, the launch loop for fixed_hip_torque
-CASES = [("free_hip", abi.F64), ("fixed_hip_simple", abi.F64), ("free_hip", abi.F32), ("fixed_hip_torque", abi.F64)]
+# (in f32 too: the f32 policy kernel)
+CASES = [("free_hip", abi.F64), ("fixed_hip_simple", abi.F64), ("free_hip", abi.F32), ("fixed_hip_torque", abi.F64),
+         ("fixed_hip_torque", abi.F32)]
 N, K = 1000, 24
 
 
