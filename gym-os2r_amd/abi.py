@@ -10,6 +10,7 @@ import ctypes as C
 from typing import Mapping, Optional
 
 ABI_VERSION = 6
+ABI_MINOR = 1    # OS2R_ABI_MINOR: os2r_rollout_policy_noisy is there
 MAX_DOF = 5
 MAX_CAND = 192
 MAX_OBS = 12
@@ -32,6 +33,9 @@ DONE_BIT, TRUNCATED_BIT, NONFINITE_BIT = 1, 2, 4
 
 # os2r_rollout_policy flags (include/os2r.h): per-env weights, tanh squash (else clip), sums over the first episode only
 POLICY_PER_ENV, POLICY_TANH, POLICY_FIRST_EPISODE = 1, 2, 4
+# os2r_rollout_policy_noisy only: sigma per environment ([2][N]); the random stream of its noise
+POLICY_SIGMA_PER_ENV = 8
+STREAM_POLICY_NOISE = 5
 
 # solver defaults (config_struct): sweeps only / with the exact finish
 DEFAULT_PGS_ITERS, DEFAULT_PGS_EXACT = 20, 12

@@ -405,11 +405,14 @@ int dev_alloc(Os2rSim* s, void** p, size_t bytes) {
 // accumulation of the step's reward and done flag (same results)
 template <typename T>
 int do_rollout_policy(Os2rSim* s, int K, const void* w, int flags, void* ret, int32_t* len, void* obs, void* reward, uint8_t* done,
-                      void* term, uint16_t* reason, hipStream_t st) {
+                      void* term, uint16_t* reason, hipStream_t st, const void* sigma = nullptr, uint32_t salt = 0u,
+                      void* act_out = nullptr, void* eps_out = nullptr) {
   const size_t N = (size_t)s->cfg.num_envs, D = (size_t)s->D;
   PolicyArgs<T> p;
   std::memset(&p, 0, sizeof(p));
   p.w = (const T*)w; p.flags = flags; p.ret = (T*)ret; p.len = len;
+  // exploration noise (os2r_rollout_policy_noisy): a null sigma is the deterministic policy
+  p.sigma = (const T*)sigma; p.salt = salt; p.act_out = (T*)act_out; p.eps_out = (T*)eps_out;
   if (!s->jit && !s->counters) {
     p.s = make_args<T>(s);
     p.s.obs = (T*)obs; p.s.reward = (T*)reward; p.s.done = done; p.s.term_obs = (T*)term; p.s.reason = reason;
@@ -431,7 +434,9 @@ int do_rollout_policy(Os2rSim* s, int K, const void* w, int flags, void* ret, in
   uint8_t* const mask_keep = s->done_mask;
   s->done_mask = nullptr;
   for (int k = 0; k < K && rc == OS2R_OK; ++k) {
-    p.s = make_args<T>(s);
+    p.s = make_args<T>(s);   // (with it the step counter of env-step k, which keys the noise)
+    p.act_out = act_out ? (T*)act_out + (size_t)k * N * 2 : nullptr;
+    p.eps_out = eps_out ? (T*)eps_out + (size_t)k * N * 2 : nullptr;
     if (Launcher<T>::policy(s->nq, p, st) != 0) { s->err = "no policy kernel for this chain length"; rc = OS2R_ERR_INVALID; break; }
     // the sums need the step's reward and done flag: the handle's scratch outputs stand in for the ones not asked for
     T* const rew_k = reward ? (T*)reward + (size_t)k * N : (T*)s->b_rew;
@@ -472,6 +477,7 @@ int param_view(Os2rSim* s, int field, void** base, int* count) {
 extern "C" {
 
 int os2r_abi_version(void) { return OS2R_ABI_VERSION; }
+int os2r_abi_minor(void) { return OS2R_ABI_MINOR; }
 
 int os2r_create(const Os2rConfig* cfg, Os2rSim** out) {
   if (!out) { g_create_error = "null out pointer"; return OS2R_ERR_INVALID; }
@@ -609,6 +615,26 @@ int os2r_rollout_policy(Os2rSim* sim, int nsteps, const void* weights_dev, int32
   return sim->cfg.dtype == OS2R_F64
              ? do_rollout_policy<double>(sim, nsteps, weights_dev, flags, return_dev, length_dev, obs_dev, reward_dev, done_dev, term_obs_dev, reason_dev, st)
              : do_rollout_policy<float>(sim, nsteps, weights_dev, flags, return_dev, length_dev, obs_dev, reward_dev, done_dev, term_obs_dev, reason_dev, st);
+}
+
+int os2r_rollout_policy_noisy(Os2rSim* sim, int nsteps, const void* weights_dev, int32_t flags, const void* sigma_dev, uint32_t salt,
+                              void* return_dev, int32_t* length_dev, void* obs_dev, void* reward_dev, uint8_t* done_dev,
+                              void* term_obs_dev, uint16_t* reason_dev, void* action_dev, void* noise_dev, void* stream) {
+  if (!sim) return OS2R_ERR_INVALID;
+  if (nsteps < 1) { sim->err = "os2r_rollout_policy_noisy: nsteps must be >= 1"; return OS2R_ERR_INVALID; }
+  if (!weights_dev) { sim->err = "os2r_rollout_policy_noisy: null weights"; return OS2R_ERR_INVALID; }
+  if (!sigma_dev) { sim->err = "os2r_rollout_policy_noisy: null sigma"; return OS2R_ERR_INVALID; }
+  if (flags & ~(OS2R_POLICY_PER_ENV | OS2R_POLICY_TANH | OS2R_POLICY_FIRST_EPISODE | OS2R_POLICY_SIGMA_PER_ENV)) {
+    sim->err = "os2r_rollout_policy_noisy: unknown flag bits";
+    return OS2R_ERR_INVALID;
+  }
+  DeviceGuard guard(sim->cfg.device);
+  hipStream_t st = (hipStream_t)stream;
+  return sim->cfg.dtype == OS2R_F64
+             ? do_rollout_policy<double>(sim, nsteps, weights_dev, flags, return_dev, length_dev, obs_dev, reward_dev, done_dev, term_obs_dev,
+                                         reason_dev, st, sigma_dev, salt, action_dev, noise_dev)
+             : do_rollout_policy<float>(sim, nsteps, weights_dev, flags, return_dev, length_dev, obs_dev, reward_dev, done_dev, term_obs_dev,
+                                        reason_dev, st, sigma_dev, salt, action_dev, noise_dev);
 }
 
 int os2r_get_state(Os2rSim* sim, void* q_dev, void* qd_dev, void* stream) {

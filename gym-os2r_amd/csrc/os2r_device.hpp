@@ -297,7 +297,7 @@ struct StModel {
 // counter RNG: Philox4x32-10 (Salmon et al., SC'11).  Streams and counters are part of the
 // stepper's specification (DESIGN.md "Random streams").
 // ----------------------------------------------------------------------------------------
-enum { kStreamAction = 1, kStreamReset = 2, kStreamParams = 3, kStreamGravity = 4 };
+enum { kStreamAction = 1, kStreamReset = 2, kStreamParams = 3, kStreamGravity = 4, kStreamPolicyNoise = 5 };
 
 __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
                                                uint32_t k0, uint32_t k1, uint32_t (&out)[4]) {

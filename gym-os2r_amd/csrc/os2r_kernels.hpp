@@ -396,17 +396,21 @@ struct PolicyArgs {
   int32_t* __restrict__ len; // [N] or null: env-steps summed
   T* __restrict__ act;       // launch loop only: [N][2] actions the policy kernel hands to the step launch
   uint8_t* __restrict__ open;// launch loop only: [N] 1 while the environment's returns are still summed
+  // os2r_rollout_policy_noisy (appended: the StepArgs stay at offset 0, the fields above where they were)
+  const T* __restrict__ sigma;   // null: the deterministic policy; [2] shared, or [2][N] (OS2R_POLICY_SIGMA_PER_ENV)
+  T* __restrict__ act_out;       // nullable: applied actions, [K][N][2] (fused) / step k's [N][2] slice (launch loop)
+  T* __restrict__ eps_out;       // nullable: the noise eps, same shape
+  uint32_t salt;                 // enters the noise counter: c1 = (c >> 32) ^ salt
 };
 
 // The one policy function of both paths (fused rollout, launch loop).  Evaluation order is part of the contract
 // (include/os2r.h): z_j = (((b_j + W_j0*o_0) + W_j1*o_1) + ...), each product rounded on its own.  Shared weights are
 // wave-uniform (scalar loads); per-env ones are [2(D+1)][N] and load coalesced.
 template <typename T>
-__device__ __forceinline__ void policy_action(const T* __restrict__ w, int flags, int D, long long N, long long e,
-                                              const T (&obs)[OS2R_MAX_OBS], T& ax, T& ay) {
+__device__ __forceinline__ void policy_presquash(const T* __restrict__ w, int flags, int D, long long N, long long e,
+                                                 const T (&obs)[OS2R_MAX_OBS], T (&z)[2]) {
 #pragma clang fp contract(off)
   const int R = D + 1;
-  T z[2];
   if (flags & OS2R_POLICY_PER_ENV) {
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
@@ -426,12 +430,58 @@ __device__ __forceinline__ void policy_action(const T* __restrict__ w, int flags
       z[j] = acc;
     }
   }
+}
+
+template <typename T>
+__device__ __forceinline__ void policy_squash(int flags, T (&z)[2]) {
   if (flags & OS2R_POLICY_TANH) {
     z[0] = tanh_t(z[0]);
     z[1] = tanh_t(z[1]);
   } else {
 #pragma unroll
     for (int j = 0; j < 2; ++j) z[j] = z[j] < T(-1) ? T(-1) : (z[j] > T(1) ? T(1) : z[j]);
+  }
+}
+
+// Exploration noise (os2r_rollout_policy_noisy): one Philox block of stream 5 keyed by (seed, global environment index, step
+// counter c, salt) gives the two normals of hip and knee -- evaluated in double in the fp32 kernels too, then rounded once, so
+// that both dtypes share one noise stream --; y_j = z_j + (sigma_j * eps_j), the product rounded on its own.
+template <typename T>
+__device__ __forceinline__ void policy_noise(const T* __restrict__ sigma, int flags, long long N, long long e,
+                                             unsigned long long seed, uint32_t genv, unsigned long long c, uint32_t salt,
+                                             T (&z)[2], T (&eps)[2]) {
+#pragma clang fp contract(off)
+  double n0, n1;
+  normal2(seed, genv, kStreamPolicyNoise, (uint32_t)c, (uint32_t)(c >> 32) ^ salt, n0, n1);
+  eps[0] = (T)n0;
+  eps[1] = (T)n1;
+  const bool per_env = (flags & OS2R_POLICY_SIGMA_PER_ENV) != 0;
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const T sg = per_env ? sigma[(long long)j * N + e] : sigma[j];
+    const T d = sg * eps[j];
+    z[j] = z[j] + d;
+  }
+}
+
+// a = squash(z + sigma * eps) of environment e (lane `valid`: not a shadow lane of a tail wave) in the env-step with counter c;
+// with P.sigma the action and the noise go to act_out / eps_out + 2 * at (nullable).  The branch on P.sigma is wave-uniform.
+template <typename T>
+__device__ __forceinline__ void policy_action(const PolicyArgs<T>* P, const StepArgs<T>& A, int D, long long e, bool valid,
+                                              unsigned long long c, long long at, const T (&obs)[OS2R_MAX_OBS], T& ax, T& ay) {
+  const int flags = P->flags;
+  T z[2];
+  policy_presquash<T>(P->w, flags, D, A.N, e, obs, z);
+  if (P->sigma) {
+    T eps[2];
+    policy_noise<T>(P->sigma, flags, A.N, e, A.seed, (uint32_t)(A.env_offset + e), c, P->salt, z, eps);
+    policy_squash<T>(flags, z);
+    if (valid) {
+      if (P->act_out) { P->act_out[2 * at] = z[0]; P->act_out[2 * at + 1] = z[1]; }
+      if (P->eps_out) { P->eps_out[2 * at] = eps[0]; P->eps_out[2 * at + 1] = eps[1]; }
+    }
+  } else {
+    policy_squash<T>(flags, z);
   }
   ax = z[0];
   ay = z[1];
@@ -567,7 +617,8 @@ __device__ __forceinline__ void step_body(const StepArgs<T>& A) {
       bool dn0;
       unsigned why0;
       observe<T, NQ, LAY>(ts, q, qd, h2x, h2y, o, dn0, why0);
-      policy_action<T>(pa->w, pa->flags, D, A.N, e, o, ax, ay);
+      // (with sigma: the noise is drawn and a, eps of step k are stored here by the owning lane: nothing of it lives on)
+      policy_action<T>(pa, A, D, e, valid, step_count, ko + e, o, ax, ay);
     } else if (A.actions) {
       ax = A.actions[2 * (ko + e)];
       ay = A.actions[2 * (ko + e) + 1];
@@ -795,7 +846,7 @@ __global__ __launch_bounds__(kWave) void policy_kernel(const PolicyArgs<T> P) {
   unsigned why;
   observe<T, NQ>(ts, q, qd, h2x, h2y, obs, dn, why);
   T ax, ay;
-  policy_action<T>(P.w, P.flags, ts->obs_dim, A.N, e, obs, ax, ay);
+  policy_action<T>(&P, A, ts->obs_dim, e, valid, A.step_count, e, obs, ax, ay);
   if (valid) {
     P.act[2 * e] = ax;
     P.act[2 * e + 1] = ay;

@@ -20,6 +20,7 @@ PYBIND11_MODULE(_os2r_py, m) {
   m.doc() = "pybind11 binding of libos2r.so (MI355X batched monopod stepper)";
   const auto nogil = py::call_guard<py::gil_scoped_release>();
   m.def("abi_version", &os2r_abi_version);
+  m.def("abi_minor", &os2r_abi_minor);
   m.def("create", [](addr cfg) {
     Os2rSim* s = nullptr;
     int rc;
@@ -36,6 +37,10 @@ PYBIND11_MODULE(_os2r_py, m) {
                              addr st) {
     return os2r_rollout_policy(H(h), n, P(w), flags, P(ret), (int32_t*)P(len), P(obs), P(rew), (uint8_t*)P(done), P(term),
                                (uint16_t*)P(why), P(st)); }, nogil);
+  m.def("rollout_policy_noisy", [](addr h, int n, addr w, int flags, addr sigma, uint32_t salt, addr ret, addr len, addr obs, addr rew,
+                                   addr done, addr term, addr why, addr act, addr eps, addr st) {
+    return os2r_rollout_policy_noisy(H(h), n, P(w), flags, P(sigma), salt, P(ret), (int32_t*)P(len), P(obs), P(rew), (uint8_t*)P(done),
+                                     P(term), (uint16_t*)P(why), P(act), P(eps), P(st)); }, nogil);
   m.def("get_solver_state", [](addr h, addr l, addr f, addr st) { return os2r_get_solver_state(H(h), P(l), (uint32_t*)P(f), P(st)); }, nogil);
   m.def("set_solver_state", [](addr h, addr l, addr f, addr st) { return os2r_set_solver_state(H(h), P(l), (const uint32_t*)P(f), P(st)); }, nogil);
   m.def("get_state", [](addr h, addr q, addr qd, addr st) { return os2r_get_state(H(h), P(q), P(qd), P(st)); }, nogil);

@@ -68,6 +68,11 @@ class _PybindLib:
         return self.m.rollout_policy(self._a(h), int(n), self._a(w), int(flags), self._a(ret), self._a(length), self._a(obs),
                                      self._a(rew), self._a(done), self._a(term), self._a(reason), self._a(st))
 
+    def os2r_rollout_policy_noisy(self, h, n, w, flags, sigma, salt, ret, length, obs, rew, done, term, reason, act, eps, st):
+        return self.m.rollout_policy_noisy(self._a(h), int(n), self._a(w), int(flags), self._a(sigma), int(salt), self._a(ret),
+                                           self._a(length), self._a(obs), self._a(rew), self._a(done), self._a(term),
+                                           self._a(reason), self._a(act), self._a(eps), self._a(st))
+
     def os2r_get_action_history(self, h, w, o, st):
         return self.m.get_action_history(self._a(h), int(w), self._a(o), self._a(st))
 
@@ -257,17 +262,44 @@ class HipSim:
         self._check(self._lib.os2r_rollout(self._h, int(nsteps), _ptr(actions), _ptr(obs), _ptr(rew), _ptr(done), _ptr(term),
                                            _ptr(reasons), self._stream()), "os2r_rollout")
 
+    def _sigma(self, sigma):
+        """sigma of rollout_policy -> (contiguous tensor in the kernel's layout, flag bits)."""
+        if isinstance(sigma, bool):
+            raise ValueError("rollout_policy: sigma must be a float, a [2] tensor or an [N, 2] tensor")
+        if isinstance(sigma, (int, float)):
+            return torch.full((2,), float(sigma), dtype=self.dtype, device=self.device), 0
+        if not isinstance(sigma, torch.Tensor):
+            raise ValueError(f"rollout_policy: sigma must be a float, a [2] tensor or an [N, 2] tensor, got {type(sigma)}")
+        shape = tuple(sigma.shape)
+        if shape not in ((2,), (self.N, 2)):
+            raise ValueError(f"rollout_policy: sigma must be [2] or [{self.N}, 2], got {shape}")
+        if sigma.dtype != self.dtype or sigma.device != self.device:
+            raise ValueError(f"rollout_policy: sigma must be {self.dtype} on {self.device}, got {sigma.dtype} on {sigma.device}")
+        if shape == (2,):
+            return sigma.contiguous(), 0
+        return sigma.t().contiguous(), abi.POLICY_SIGMA_PER_ENV      # the kernel's layout: [2][N], env index fastest
+
     def rollout_policy(self, nsteps: int, weights, *, tanh: bool = False, first_episode: bool = False, want_outputs: bool = False,
-                       want_terminal: bool = False, want_reasons: bool = False):
+                       want_terminal: bool = False, want_reasons: bool = False, sigma=None, salt: int = 0,
+                       want_actions: bool = False, want_noise: bool = False):
         """`nsteps` env-steps with the linear policy a = squash(W.o + b) in the loop, evaluated on the device on every environment's
         own observation (include/os2r.h: os2r_rollout_policy; one launch where os2r_rollout has a fused kernel).
         weights: [2, D+1] shared by all environments or [N, 2, D+1] one set per environment; row j (0 hip, 1 knee) holds
         W_j0 .. W_j,D-1, b_j.  squash: clip to [-1, 1], or tanh.  first_episode: the sums stop after an environment's first
         done flag in the window.  -> (returns [N], lengths [N] int32, outputs): outputs is the rollout() tuple
-        (obs, reward, done, terminal_obs, reasons) when want_outputs, else None (nothing per step is written then)."""
+        (obs, reward, done, terminal_obs, reasons) when want_outputs, else None (nothing per step is written then).
+        sigma (a float, a [2] tensor or an [N, 2] tensor in the handle's dtype): Gaussian exploration noise, a = squash(W.o + b +
+        sigma * eps) with eps ~ N(0, 1) a pure function of (seed, global env index, step counter, salt) (include/os2r.h:
+        os2r_rollout_policy_noisy); the call then returns a fourth element (actions [K, N, 2] if want_actions else None,
+        noise eps [K, N, 2] if want_noise else None): rollout(K, actions) replays the window bit for bit."""
         K = int(nsteps)
         if K < 1:
             raise ValueError("rollout_policy: nsteps must be >= 1")
+        if sigma is None and (want_actions or want_noise or salt):
+            raise ValueError("rollout_policy: want_actions, want_noise and salt need sigma (sigma=0.0: the deterministic policy)")
+        if not 0 <= int(salt) < 2 ** 32:
+            raise ValueError("rollout_policy: salt must be a 32-bit unsigned value")
+        sg, sg_flags = (None, 0) if sigma is None else self._sigma(sigma)
         R = self.D + 1
         if not isinstance(weights, torch.Tensor):
             weights = torch.as_tensor(weights)
@@ -290,6 +322,13 @@ class HipSim:
             done = self._new(K, self.N, dtype=torch.uint8)
             term = self._new(K, self.N, self.D) if want_terminal else None
             why = self._new(K, self.N, dtype=torch.int16) if want_reasons else None
+        if sg is not None:
+            act = self._new(K, self.N, 2) if want_actions else None
+            eps = self._new(K, self.N, 2) if want_noise else None
+            self._check(self._lib.os2r_rollout_policy_noisy(self._h, K, _ptr(w), flags | sg_flags, _ptr(sg), int(salt), _ptr(ret),
+                                                            _ptr(length), _ptr(obs), _ptr(rew), _ptr(done), _ptr(term), _ptr(why),
+                                                            _ptr(act), _ptr(eps), self._stream()), "os2r_rollout_policy_noisy")
+            return ret, length, ((obs, rew, done, term, why) if want_outputs else None), (act, eps)
         self._check(self._lib.os2r_rollout_policy(self._h, K, _ptr(w), flags, _ptr(ret), _ptr(length), _ptr(obs), _ptr(rew),
                                                   _ptr(done), _ptr(term), _ptr(why), self._stream()), "os2r_rollout_policy")
         return ret, length, ((obs, rew, done, term, why) if want_outputs else None)

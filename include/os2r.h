@@ -40,6 +40,7 @@ extern "C" {
 #endif
 
 #define OS2R_ABI_VERSION 6   /* os2r_create also takes configs stamped 5 (Os2rConfig did not change in 6) */
+#define OS2R_ABI_MINOR 1     /* entry points added within ABI 6 (os2r_abi_minor): 1: os2r_rollout_policy_noisy */
 
 #define OS2R_MAX_DOF 5      /* yaw, pitch, boom_connector, hip, knee                       */
 #define OS2R_MAX_CAND 192   /* ground-contact candidate points of one model                */
@@ -206,6 +207,7 @@ enum {
 typedef struct Os2rSim Os2rSim;
 
 OS2R_API int os2r_abi_version(void);
+OS2R_API int os2r_abi_minor(void);   /* OS2R_ABI_MINOR of the built library: a binding asks it whether an entry point is there */
 
 /* Allocates device state for cfg->num_envs environments, initialises per-env
  * parameters to the model's nominal values (gravity: N(mean,std) per env when
@@ -273,6 +275,32 @@ OS2R_API int os2r_rollout_policy(Os2rSim* sim, int nsteps, const void* weights_d
                                  void* return_dev, int32_t* length_dev,
                                  void* obs_dev, void* reward_dev, uint8_t* done_dev, void* term_obs_dev,
                                  uint16_t* reason_dev, void* stream);
+
+/* The same rollout with Gaussian exploration noise on the policy's pre-squash output (ABI 6, minor 1).  In env-step k of the
+ * window, with c = step counter + k (os2r_get_step_count before the call) and e the environment's local index:
+ *   (u0, u1) = the two 53-bit uniforms of the Philox4x32-10 block with counter {env_offset + e, 5, c0, c1} and key = seed, where
+ *              c0 = low 32 bits of c and c1 = (c >> 32) ^ salt: random stream 5, one block per environment and env-step
+ *   eps_0    = sqrt(-2 log(1 - u0)) * cos(2 pi u1), eps_1 = sqrt(-2 log(1 - u0)) * sin(2 pi u1), evaluated in double and
+ *              rounded once to the handle's dtype: an f32 handle draws the f64 handle's noise, rounded
+ *   y_j      = z_j + (sigma_j * eps_j), z_j as above; the product is rounded on its own, then one add
+ *   a_j      = min(max(y_j, -1), 1), or tanh(y_j): noisy actions are squashed, so they are never counted as violations
+ * The noise is a pure function of (seed, global environment index, step counter, salt): shards of one batch, a restored
+ * checkpoint and windows split differently draw the same noise; another salt draws independent noise at the same step
+ * counter (two evaluations from one checkpoint).  sigma_j = 0 gives the deterministic action.  The handle advances exactly
+ * as `nsteps` calls of os2r_step(actions = a) would: os2r_rollout on the reported actions replays the window bit for bit.
+ *   sigma_dev   handle's dtype: [2] (hip, knee) shared by all environments, or [2][num_envs] (env index fastest) with
+ *               OS2R_POLICY_SIGMA_PER_ENV
+ *   salt        any 32-bit value; the same salt reproduces the same noise
+ *   action_dev  [nsteps][num_envs][2] handle's dtype (nullable): the applied action a
+ *   noise_dev   [nsteps][num_envs][2] handle's dtype (nullable): eps
+ * Everything else as os2r_rollout_policy, which itself refuses OS2R_POLICY_SIGMA_PER_ENV.
+ * Errors: OS2R_ERR_INVALID for nsteps < 1, a null weights_dev or sigma_dev, or an unknown flag bit.                             */
+#define OS2R_POLICY_SIGMA_PER_ENV 8 /* sigma [2][N], env index fastest; else one pair [2] for all envs (noisy entry point only) */
+OS2R_API int os2r_rollout_policy_noisy(Os2rSim* sim, int nsteps, const void* weights_dev, int32_t flags,
+                                       const void* sigma_dev, uint32_t salt,
+                                       void* return_dev, int32_t* length_dev,
+                                       void* obs_dev, void* reward_dev, uint8_t* done_dev, void* term_obs_dev,
+                                       uint16_t* reason_dev, void* action_dev, void* noise_dev, void* stream);
 
 /* Model-specialised kernels.  A robot that is not one of the four compiled-in reference variants
  * runs on generic kernels that read its constants through scalar loads (about half the speed).

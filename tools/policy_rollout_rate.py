@@ -14,6 +14,10 @@ checkpoint of that regime and times --steps env-steps of the whole batch with HI
   replayed       os2r_rollout with the actions the policy took in that window (recomputed in torch from its observations,
                  bit for bit): the open-loop launch on the same trajectory -- the cost of an env-step depends on the regime the
                  actions drive the robots into (contacts, solver rounds), so this is the line the policy is compared with
+  policy noisy   os2r_rollout_policy_noisy, shared weights and shared sigma = 0.3 (Gaussian exploration noise drawn in the kernel),
+                 per-step outputs off, or all on (obs / reward / done / applied actions / noise); its `replayed` line is
+                 os2r_rollout with the actions it reported -- noise drives the robots into another regime than the
+                 deterministic policy does, so the noisy lines are compared with that one, not with `policy`
   python loop    step_into per env-step, the policy a torch.nn.Linear(D, 2) (the shared weights) + clamp on the returned
                  observation
 """
@@ -81,6 +85,12 @@ def recorded_actions(torch, sim, ck, obs0, W, K, calls):
     return torch.stack(acts)
 
 
+def recorded_noisy_actions(torch, sim, ck, W, sigma, K, calls):
+    """[calls, K, N, 2]: the actions os2r_rollout_policy_noisy reports over `calls` calls of K env-steps from checkpoint `ck`."""
+    sim.restore(ck)
+    return torch.stack([sim.rollout_policy(K, W, sigma=sigma, want_actions=True)[3][0] for _ in range(calls)])
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=65536)
@@ -101,6 +111,7 @@ def main():
     g = torch.Generator(device=sim.device).manual_seed(1)
     w_shared = 0.3 * torch.randn(2, D + 1, dtype=dt, device=sim.device, generator=g)
     w_env = 0.3 * torch.randn(N, 2, D + 1, dtype=dt, device=sim.device, generator=g)
+    sigma = torch.full((2,), 0.3, dtype=dt, device=sim.device)
 
     if args.only == "policy10":
         for _ in range(1 + args.steps // 10):
@@ -131,6 +142,15 @@ def main():
                 timed(torch, sim, ck, lambda i: sim.rollout_policy(K, w), calls, args.reps), calls * K)
             row(f"rollout_policy {wname}, outputs on", K,
                 timed(torch, sim, ck, lambda i: sim.rollout_policy(K, w, want_outputs=True), calls, args.reps), calls * K)
+        acts = recorded_noisy_actions(torch, sim, ck, w_shared, sigma, K, calls)
+        row("rollout, replayed noisy shared policy", K,
+            timed(torch, sim, ck, lambda i: sim.rollout_into(K, acts[i], obs, rew, done), calls, args.reps), calls * K)
+        del acts
+        row("rollout_policy noisy shared, outputs off", K,
+            timed(torch, sim, ck, lambda i: sim.rollout_policy(K, w_shared, sigma=sigma), calls, args.reps), calls * K)
+        row("rollout_policy noisy shared, all outputs on", K,
+            timed(torch, sim, ck, lambda i: sim.rollout_policy(K, w_shared, sigma=sigma, want_outputs=True, want_actions=True,
+                                                               want_noise=True), calls, args.reps), calls * K)
         del obs, rew, done
 
     lin = torch.nn.Linear(D, 2).to(sim.device, dt)
