@@ -36,6 +36,8 @@ POLICY_PER_ENV, POLICY_TANH, POLICY_FIRST_EPISODE = 1, 2, 4
 # os2r_rollout_policy_noisy only: sigma per environment ([2][N]); the random stream of its noise
 POLICY_SIGMA_PER_ENV = 8
 STREAM_POLICY_NOISE = 5
+# os2r_copy_envs: which arrays of an environment move (include/os2r.h)
+COPY_STATE, COPY_PARAMS = 1, 2
 
 # solver defaults (config_struct): sweeps only / with the exact finish
 DEFAULT_PGS_ITERS, DEFAULT_PGS_EXACT = 20, 12

@@ -116,6 +116,7 @@ struct SimBase {
   unsigned long long* debug = nullptr;  // diagnostic stamp builds only
   void* pol_act = nullptr;              // os2r_rollout_policy's launch loop: [N][2] actions, allocated on first use ...
   uint8_t* pol_open = nullptr;          // ... and [N] "still summing" flags
+  void* copy_stage = nullptr;           // os2r_copy_envs within one handle: every copied row once, allocated on first use
 };
 
 }  // namespace
@@ -452,6 +453,74 @@ int do_rollout_policy(Os2rSim* s, int K, const void* w, int flags, void* ret, in
   return rc;
 }
 
+// The rows `what` selects, as the copy kernel takes them: row r of an array of the source next to row r of the same array of the
+// destination.  `stage` (the in-place case) stands in for the destination (to_stage) or for the source: it holds every row
+// once, [row][num_envs of the handle], the 32-bit rows and the pose bytes behind the rows of the handle's dtype.
+template <typename T>
+CopyArgs<T> copy_rows(Os2rSim* d, Os2rSim* s, int what, void* stage, bool to_stage) {
+  CopyArgs<T> a;
+  std::memset(&a, 0, sizeof(a));
+  const long long Nd = d->cfg.num_envs, Ns = s->cfg.num_envs;
+  a.Nd = Nd; a.Ns = Ns; a.gather = 1;
+  const int nq = d->nq;
+  T* const stage_t = (T*)stage;
+  uint32_t* const stage_w = (uint32_t*)(stage_t + (size_t)(10 * nq + 5) * (size_t)Nd);
+  auto rows = [&](const void* sp, void* dp, int count) {
+    for (int r = 0; r < count; ++r, ++a.nrows) {
+      a.src[a.nrows] = stage && !to_stage ? stage_t + (size_t)a.nrows * Nd : (const T*)sp + (size_t)r * Ns;
+      a.dst[a.nrows] = stage && to_stage ? stage_t + (size_t)a.nrows * Nd : (T*)dp + (size_t)r * Nd;
+    }
+  };
+  auto words = [&](const void* sp, void* dp) {
+    a.src32[a.nwords] = stage && !to_stage ? stage_w + (size_t)a.nwords * Nd : (const uint32_t*)sp;
+    a.dst32[a.nwords] = stage && to_stage ? stage_w + (size_t)a.nwords * Nd : (uint32_t*)dp;
+    ++a.nwords;
+  };
+  if (what & OS2R_COPY_STATE) {
+    rows(s->q, d->q, nq); rows(s->qd, d->qd, nq); rows(s->hist, d->hist, 4); rows(s->solver_l, d->solver_l, 4 * nq);
+    words(s->solver_flags, d->solver_flags); words(s->steps, d->steps); words(s->episode, d->episode);
+    uint8_t* const stage_b = (uint8_t*)(stage_w + 3 * (size_t)Nd);
+    a.src8 = stage && !to_stage ? stage_b : s->pose;
+    a.dst8 = stage && to_stage ? stage_b : d->pose;
+  }
+  if (what & OS2R_COPY_PARAMS) {
+    rows(s->mass_scale, d->mass_scale, nq); rows(s->damping, d->damping, nq); rows(s->friction, d->friction, nq);
+    rows(s->mu, d->mu, nq); rows(s->gravity, d->gravity, 1);
+  }
+  return a;
+}
+
+template <typename T>
+int do_copy(Os2rSim* d, Os2rSim* s, const int32_t* index, int what, void* obs, hipStream_t st) {
+  if (d != s) {
+    CopyArgs<T> a = copy_rows<T>(d, s, what, nullptr, false);
+    a.index = index;
+    Launcher<T>::copy_envs(a, st);
+  } else if (index) {
+    // within one handle all reads precede all writes: gather into the staging rows, then copy the same lanes back
+    if (!d->copy_stage) {
+      const size_t N = (size_t)d->cfg.num_envs;
+      const int rc = dev_alloc(d, &d->copy_stage, ((size_t)(10 * d->nq + 5) * d->esz + 3 * 4 + 1) * N);
+      if (rc) return rc;
+    }
+    CopyArgs<T> a = copy_rows<T>(d, s, what, d->copy_stage, true);
+    a.index = index;
+    Launcher<T>::copy_envs(a, st);
+    a = copy_rows<T>(d, s, what, d->copy_stage, false);
+    a.index = index; a.gather = 0;
+    Launcher<T>::copy_envs(a, st);
+  }
+  if (d != s && (what & OS2R_COPY_PARAMS) && (s->dr || s->cfg.model.gravity_z != d->cfg.model.gravity_z))
+    d->dr = true;   // as after os2r_set_params: the step kernels read the parameter arrays per lane from now on
+  if (obs) {
+    StepArgs<T> a = make_args<T>(d);
+    a.obs = (T*)obs;
+    if (Launcher<T>::copy_obs(d->nq, a, st) != 0) { d->err = "os2r_copy_envs: no observation kernel for this chain length"; return OS2R_ERR_INVALID; }
+  }
+  HIP_TRY(d, hipGetLastError());
+  return OS2R_OK;
+}
+
 void free_all(Os2rSim* s) {
   for (void* p : s->allocs) (void)hipFree(p);
   s->allocs.clear();
@@ -635,6 +704,25 @@ int os2r_rollout_policy_noisy(Os2rSim* sim, int nsteps, const void* weights_dev,
                                          reason_dev, st, sigma_dev, salt, action_dev, noise_dev)
              : do_rollout_policy<float>(sim, nsteps, weights_dev, flags, return_dev, length_dev, obs_dev, reward_dev, done_dev, term_obs_dev,
                                         reason_dev, st, sigma_dev, salt, action_dev, noise_dev);
+}
+
+int os2r_copy_envs(Os2rSim* dst, Os2rSim* src, const int32_t* index_dev, int32_t what, void* obs_dev, void* stream) {
+  if (!dst) { g_create_error = "os2r_copy_envs: null destination handle"; return OS2R_ERR_INVALID; }
+  if (!src) { dst->err = "os2r_copy_envs: null source handle"; return OS2R_ERR_INVALID; }
+  if (what == 0 || (what & ~(OS2R_COPY_STATE | OS2R_COPY_PARAMS))) {
+    dst->err = what == 0 ? "os2r_copy_envs: nothing selected (what == 0)" : "os2r_copy_envs: unknown bits in what";
+    return OS2R_ERR_INVALID;
+  }
+  if (src->cfg.dtype != dst->cfg.dtype) { dst->err = "os2r_copy_envs: source and destination differ in dtype"; return OS2R_ERR_INVALID; }
+  if (src->cfg.device != dst->cfg.device) { dst->err = "os2r_copy_envs: source and destination are on different devices"; return OS2R_ERR_INVALID; }
+  if (!os2r::same_model(src->cfg.model, dst->cfg.model)) { dst->err = "os2r_copy_envs: source and destination are different robot models"; return OS2R_ERR_INVALID; }
+  if (!index_dev && src->cfg.num_envs != dst->cfg.num_envs) {
+    dst->err = "os2r_copy_envs: the identity map (null index) needs equal num_envs";
+    return OS2R_ERR_INVALID;
+  }
+  DeviceGuard guard(dst->cfg.device);
+  return dst->cfg.dtype == OS2R_F64 ? do_copy<double>(dst, src, index_dev, what, obs_dev, (hipStream_t)stream)
+                                    : do_copy<float>(dst, src, index_dev, what, obs_dev, (hipStream_t)stream);
 }
 
 int os2r_get_state(Os2rSim* sim, void* q_dev, void* qd_dev, void* stream) {

@@ -933,6 +933,96 @@ __global__ void fill_kernel(T* __restrict__ dst, long long n, T value) {
   if (i < n) dst[i] = value;
 }
 
+// ----------------------------------------------------------------------------------------
+// os2r_copy_envs: environment e of the destination becomes environment index[e] of the source
+// ----------------------------------------------------------------------------------------
+// Pure memory movement, the opposite corner from the step kernel: no arithmetic, a dozen registers, as many waves per
+// SIMD as the hardware holds.  Every array of a handle is SoA [rows][N]; the host lists the selected rows of both handles
+// in one flat table (they live in a dozen allocations), and the grid's second dimension walks it kCopyGroup rows at a
+// time: a lane issues the loads of its group, then the stores, so a wave has kCopyGroup requests in flight and a small
+// batch still fills the machine (256 envs: 4 x 8 waves instead of 4).  Row r is read at src[r][i] and stored at
+// dst[r][e]: stores are always coalesced, loads are coalesced for the identity map and one address per wave for a fork.
+constexpr int kCopyMaxRows = 10 * OS2R_MAX_DOF + 5;   // q, qd: nq each; history: 4; solver impulses: 4 nq; parameters: 4 nq + 1
+constexpr int kCopyGroup = 8;
+constexpr int kCopyTable = (kCopyMaxRows + kCopyGroup - 1) / kCopyGroup * kCopyGroup;   // whole groups: a group's addresses are one fetch
+template <typename T>
+struct CopyArgs {
+  const int32_t* index;   // [Nd] or null (identity: Ns == Nd)
+  long long Nd, Ns;       // environments of the destination / the source
+  int gather;             // 1: lane e reads column index[e]; 0: column e, the index only says which lanes take part
+  int nrows;              // rows of the handle's dtype
+  int nwords;             // 32-bit rows: solver flags, elapsed steps, episode index
+  const T* src[kCopyTable];
+  T* dst[kCopyTable];
+  const uint32_t* src32[3];
+  uint32_t* dst32[3];
+  const uint8_t* src8;    // the reset pose id, or null
+  uint8_t* dst8;
+};
+
+template <typename T>
+__global__ __launch_bounds__(kWave) void copy_envs_kernel(const CopyArgs<T> A) {
+  const long long e = (long long)blockIdx.x * kWave + threadIdx.x;
+  if (e >= A.Nd) return;
+  long long i = e;
+  if (A.index) {
+    const long long ix = A.index[e];
+    if (ix < 0 || ix >= A.Ns) return;   // "keep": nothing of this environment is read or written
+    if (A.gather) i = ix;
+  }
+  const int r0 = (int)blockIdx.y * kCopyGroup;
+  if (r0 < A.nrows) {
+    const T* sp[kCopyGroup];
+    T* dp[kCopyGroup];
+    T v[kCopyGroup];
+#pragma unroll
+    for (int k = 0; k < kCopyGroup; ++k) {   // (past nrows the table holds nulls, which are fetched and never used)
+      sp[k] = A.src[r0 + k];
+      dp[k] = A.dst[r0 + k];
+    }
+#pragma unroll
+    for (int k = 0; k < kCopyGroup; ++k)
+      if (r0 + k < A.nrows) v[k] = sp[k][i];
+#pragma unroll
+    for (int k = 0; k < kCopyGroup; ++k)
+      if (r0 + k < A.nrows) dp[k][e] = v[k];
+  } else {   // the last group: the integer rows
+    uint32_t w[3];
+    uint8_t b = 0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+      if (k < A.nwords) w[k] = A.src32[k][i];
+    if (A.src8) b = A.src8[i];
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+      if (k < A.nwords) A.dst32[k][e] = w[k];
+    if (A.src8) A.dst8[e] = b;
+  }
+}
+
+// the observation of every environment's stored state, [N][D]: observe() as reset_kernel and policy_kernel evaluate it
+template <typename T, int NQ>
+__global__ __launch_bounds__(kWave) void copy_envs_obs_kernel(const StepArgs<T> A) {
+  __shared__ T tile[kWave * OS2R_MAX_OBS];
+  const int lane = threadIdx.x;
+  const long long e0 = (long long)blockIdx.x * kWave;
+  const bool valid = e0 + lane < A.N;
+  const long long e = valid ? e0 + lane : A.N - 1;
+  const TaskPtr<T> ts = as_const(A.task);
+  T q[NQ], qd[NQ];
+#pragma unroll
+  for (int i = 0; i < NQ; ++i) {
+    q[i] = A.q[i * A.N + e];
+    qd[i] = A.qd[i * A.N + e];
+  }
+  const T h1x = A.hist[2 * A.N + e], h1y = A.hist[3 * A.N + e];
+  T obs[OS2R_MAX_OBS];
+  bool dn;
+  unsigned why;
+  observe<T, NQ>(ts, q, qd, h1x, h1y, obs, dn, why);
+  store_obs_tile<T>(A.obs, obs, ts->obs_dim, e0, A.N, lane, tile);
+}
+
 // launch tables (defined in the per-dtype instantiation units)
 template <typename T>
 struct Launcher {
@@ -946,6 +1036,9 @@ struct Launcher {
   static int policy(int nq, const PolicyArgs<T>& args, hipStream_t stream);
   static void accumulate(T* ret, int32_t* len, uint8_t* open, const T* rew, const uint8_t* done, long long N, int k,
                          int first_episode, hipStream_t s);
+  // os2r_copy_envs: the copy itself, and the observation of the stored state into args.obs
+  static void copy_envs(const CopyArgs<T>& args, hipStream_t s);
+  static int copy_obs(int nq, const StepArgs<T>& args, hipStream_t s);
 };
 
 }  // namespace os2r

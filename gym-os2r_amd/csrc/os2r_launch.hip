@@ -79,6 +79,22 @@ void Launcher<T>::accumulate(T* ret, int32_t* len, uint8_t* open, const T* rew, 
                      k, first_episode);
 }
 template <typename T>
+void Launcher<T>::copy_envs(const CopyArgs<T>& a, hipStream_t s) {
+  const unsigned groups = (unsigned)((a.nrows + kCopyGroup - 1) / kCopyGroup) + ((a.nwords > 0 || a.src8) ? 1u : 0u);
+  hipLaunchKernelGGL((copy_envs_kernel<T>), dim3((unsigned)((a.Nd + kWave - 1) / kWave), groups), dim3(kWave), 0, s, a);
+}
+template <typename T>
+int Launcher<T>::copy_obs(int nq, const StepArgs<T>& a, hipStream_t s) {
+  const dim3 grid((unsigned)((a.N + kWave - 1) / kWave)), block(kWave);
+  switch (nq) {
+    case 2: hipLaunchKernelGGL((copy_envs_obs_kernel<T, 2>), grid, block, 0, s, a); return 0;
+    case 3: hipLaunchKernelGGL((copy_envs_obs_kernel<T, 3>), grid, block, 0, s, a); return 0;
+    case 4: hipLaunchKernelGGL((copy_envs_obs_kernel<T, 4>), grid, block, 0, s, a); return 0;
+    case 5: hipLaunchKernelGGL((copy_envs_obs_kernel<T, 5>), grid, block, 0, s, a); return 0;
+    default: return 1;
+  }
+}
+template <typename T>
 void Launcher<T>::gravity(T* g, long long N, long long off, unsigned long long seed, double mean, double std_,
                           hipStream_t s) {
   hipLaunchKernelGGL((gravity_kernel<T>), dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, g, N, off, seed, mean, std_);

@@ -41,6 +41,8 @@ PYBIND11_MODULE(_os2r_py, m) {
                                    addr done, addr term, addr why, addr act, addr eps, addr st) {
     return os2r_rollout_policy_noisy(H(h), n, P(w), flags, P(sigma), salt, P(ret), (int32_t*)P(len), P(obs), P(rew), (uint8_t*)P(done),
                                      P(term), (uint16_t*)P(why), P(act), P(eps), P(st)); }, nogil);
+  m.def("copy_envs", [](addr dst, addr src, addr index, int what, addr obs, addr st) {
+    return os2r_copy_envs(H(dst), H(src), (const int32_t*)P(index), what, P(obs), P(st)); }, nogil);
   m.def("get_solver_state", [](addr h, addr l, addr f, addr st) { return os2r_get_solver_state(H(h), P(l), (uint32_t*)P(f), P(st)); }, nogil);
   m.def("set_solver_state", [](addr h, addr l, addr f, addr st) { return os2r_set_solver_state(H(h), P(l), (const uint32_t*)P(f), P(st)); }, nogil);
   m.def("get_state", [](addr h, addr q, addr qd, addr st) { return os2r_get_state(H(h), P(q), P(qd), P(st)); }, nogil);

@@ -73,6 +73,9 @@ class _PybindLib:
                                            self._a(length), self._a(obs), self._a(rew), self._a(done), self._a(term),
                                            self._a(reason), self._a(act), self._a(eps), self._a(st))
 
+    def os2r_copy_envs(self, dst, src, index, what, obs, st):
+        return self.m.copy_envs(self._a(dst), self._a(src), self._a(index), int(what), self._a(obs), self._a(st))
+
     def os2r_get_action_history(self, h, w, o, st):
         return self.m.get_action_history(self._a(h), int(w), self._a(o), self._a(st))
 
@@ -483,6 +486,38 @@ class HipSim:
             self.set_params(f, v)
         self.set_episode_info(ck["steps"], ck["episode"], ck["pose"])
         self.step_count = ck["step_count"]
+
+    # -- fork / resample -------------------------------------------------------------------
+    def copy_envs_from(self, src: "HipSim", index=None, *, state: bool = True, params: bool = True, want_obs: bool = False,
+                       check: bool = False):
+        """Environment e of this handle becomes environment index[e] of `src` in one launch (include/os2r.h: os2r_copy_envs):
+        fork one environment into many, resample a population, permute, or take over a whole batch.
+        index: None (the identity map: equal sizes), an int (every environment becomes that one of `src`; the index tensor is
+        made once and kept), or an int32 [N] tensor on this device, passed by address; a negative entry keeps the environment
+        as it is, and so does an entry >= src.N (check=True looks for those on the host -- one synchronisation -- and raises
+        ValueError instead).  state / params: which arrays move (abi.COPY_STATE / abi.COPY_PARAMS); the step counter, the seed
+        and env_offset, the task and the solver settings stay this handle's.  `src` may be this handle.  `src` must have
+        finished its pending work on another stream before the call; on one stream the order is the call order.
+        -> the observation [N, D] of every environment after the copy (want_obs), else None."""
+        if not isinstance(src, HipSim):
+            raise ValueError(f"copy_envs_from: src must be a HipSim, got {type(src)}")
+        if isinstance(index, bool):
+            raise ValueError("copy_envs_from: index must be None, an int or an int32 tensor")
+        if isinstance(index, int):
+            if not 0 <= index < src.N:
+                raise ValueError(f"copy_envs_from: environment {index} is not one of the source's {src.N}")
+            forks = self.__dict__.setdefault("_fork_index", {})
+            if index not in forks:
+                forks[index] = torch.full((self.N,), index, dtype=torch.int32, device=self.device)
+            index = forks[index]
+        elif index is not None:
+            self._out(index, (self.N,), torch.int32, "copy_envs_from: index")
+            if check and bool((index >= src.N).any().item()):
+                raise ValueError(f"copy_envs_from: index holds entries >= the source's {src.N} environments")
+        what = (abi.COPY_STATE if state else 0) | (abi.COPY_PARAMS if params else 0)
+        obs = self._new(self.N, self.D) if want_obs else None
+        self._check(self._lib.os2r_copy_envs(self._h, src._h, _ptr(index), what, _ptr(obs), self._stream()), "os2r_copy_envs")
+        return obs
 
     def action_violations_into(self, dst: torch.Tensor, clear: bool = True):
         """Copy the running count of out-of-range caller actions into ``dst`` (one int32/uint32 element,

@@ -41,6 +41,7 @@ extern "C" {
 
 #define OS2R_ABI_VERSION 6   /* os2r_create also takes configs stamped 5 (Os2rConfig did not change in 6) */
 #define OS2R_ABI_MINOR 1     /* entry points added within ABI 6 (os2r_abi_minor): 1: os2r_rollout_policy_noisy */
+/* os2r_copy_envs was added later without a new minor: a binding finds out whether it is there by looking the symbol up */
 
 #define OS2R_MAX_DOF 5      /* yaw, pitch, boom_connector, hip, knee                       */
 #define OS2R_MAX_CAND 192   /* ground-contact candidate points of one model                */
@@ -368,6 +369,31 @@ OS2R_API int os2r_get_episode_info(Os2rSim* sim, int32_t* steps_dev, uint32_t* e
  * for bit (the reference has no save/restore, only env.seed).                                              */
 OS2R_API int os2r_set_episode_info(Os2rSim* sim, const int32_t* steps_dev, const uint32_t* episode_dev,
                           const uint8_t* pose_dev, void* stream);
+
+/* Copy whole environments between two handles, or within one, in one launch (fork, resample, broadcast, permute).
+ * For every environment e of `dst`, with i = index_dev[e]: if 0 <= i < num_envs of `src`, the arrays selected by `what` of
+ * dst[e] become those of src[i], bit for bit; any other i leaves dst[e] untouched (a negative index is the documented
+ * "keep"; an index past the source is never dereferenced).  OS2R_COPY_STATE | OS2R_COPY_PARAMS moves everything that
+ * determines an environment's future; what stays the destination's is its identity and configuration: the step counter,
+ * the seed and env_offset (which key the random streams, so clones diverge on their own under device-drawn actions or noise
+ * and replay exactly under explicit actions), the task, the solver settings and the caller-set output buffers.
+ *   index_dev  [dst num_envs] int32 device memory; NULL: the identity map (needs equal num_envs)
+ *   what       OS2R_COPY_* bits, at least one
+ *   obs_dev    nullable, [dst num_envs][dst obs_dim]: the observation of EVERY environment of `dst` after the copy, kept ones
+ *              included, under dst's task: the observation of the stored state, as the reset returns it; for equal tasks it
+ *              is, bit for bit, what the source's last step or reset returned for src[i]
+ * `src` == `dst` is allowed with any map (permutation, broadcast, partial): the result is as if all reads preceded all
+ * writes; the rows go through a buffer owned by the handle, allocated by the first such call (which synchronises for it;
+ * every later call allocates nothing).  The two handles must agree in dtype, device and robot (Os2rModel equal bit for bit,
+ * gravity_z excluded, as for os2r_register_model_kernels); num_envs, task, reward, auto_reset, solver settings and env_offset
+ * may differ.  After a copy of parameters from a handle with per-environment parameters (or another gravity) the
+ * destination's kernels read the parameter arrays per lane, as after os2r_set_params.  Stream-ordered on `stream`; the
+ * caller orders src's pending work before it.  Nothing synchronises the host.
+ * Errors: OS2R_ERR_INVALID for a null handle (null dst: os2r_last_error(NULL)), what == 0 or an unknown bit, a dtype, device
+ * or model mismatch, or the identity map with unequal num_envs; os2r_last_error(dst) names the cause.                       */
+#define OS2R_COPY_STATE 1   /* q, qd, action history 0 and 1, solver impulses and flags, elapsed steps, episode index, pose id */
+#define OS2R_COPY_PARAMS 2  /* mass_scale, damping, friction, mu, gravity */
+OS2R_API int os2r_copy_envs(Os2rSim* dst, Os2rSim* src, const int32_t* index_dev, int32_t what, void* obs_dev, void* stream);
 
 /* Global step counter that keys the on-device action RNG. */
 OS2R_API int os2r_get_step_count(Os2rSim* sim, uint64_t* out);
