@@ -225,6 +225,16 @@ void fill_task(const Os2rConfig& cfg, DevTask<T>& d) {
   for (int i = 0; i < OS2R_MAX_DOF; ++i) d.nominal_damping[i] = cfg.model.damping[i];
 }
 
+// The library is built with -fno-honor-nans -fno-honor-infinities: a comparison written to fail on a NaN, `!(x > 0.0)`, is compiled
+// as if there were none, and a NaN passes it (so does std::isfinite, and a test of the bits of a double passed by value: the
+// argument itself is declared free of NaNs).  The config's doubles are therefore tested on their bit pattern first, read from
+// memory as an integer.
+__attribute__((noinline)) bool is_finite(const double* x) {
+  uint64_t b;
+  std::memcpy(&b, x, sizeof(b));
+  return ((b >> 52) & 0x7ffu) != 0x7ffu;
+}
+
 int validate(const Os2rConfig* c, std::string& why) {
   if (!c) { why = "null config"; return 1; }
   // (ABI 6 added an entry point, not a field: configs stamped 5 are the same struct)
@@ -241,7 +251,7 @@ int validate(const Os2rConfig* c, std::string& why) {
   }
   for (int i = 0; i < m.nq; ++i) {
     if (m.axis[i] < 0 || m.axis[i] > 2) { why = "joint axis must be 0,1,2"; return 1; }
-    if (!(m.mass[i] > 0.0)) { why = "body mass must be positive"; return 1; }
+    if (!is_finite(&m.mass[i]) || !(m.mass[i] > 0.0)) { why = "body mass must be positive and finite"; return 1; }
   }
   for (int k = 0; k < 2; ++k)
     if (m.act_dof[k] < 0 || m.act_dof[k] >= m.nq) { why = "act_dof out of range"; return 1; }
@@ -259,12 +269,16 @@ int validate(const Os2rConfig* c, std::string& why) {
   if (t.reward_id == OS2R_REWARD_STRAIGHT_V1 && (t.idx_hip_pos < 0 || t.idx_knee_pos < 0)) { why = "StraightV1 needs hip and knee positions"; return 1; }
   if (t.n_reset_poses < 1 || t.n_reset_poses > OS2R_MAX_RESET_POSES) { why = "n_reset_poses out of range"; return 1; }
   if (c->substeps < 1 || c->substeps > 1000) { why = "substeps out of range"; return 1; }
-  if (!(c->dt > 0.0)) { why = "dt must be positive"; return 1; }
+  if (!is_finite(&c->dt) || !(c->dt > 0.0)) { why = "dt must be positive and finite"; return 1; }
   if (c->pgs_iters < 0 || c->pgs_iters > 10000) { why = "pgs_iters out of range"; return 1; }
-  if (!(c->contact_margin >= 0.0)) { why = "contact_margin must be >= 0"; return 1; }
+  if (!is_finite(&c->contact_margin) || !(c->contact_margin >= 0.0)) { why = "contact_margin must be >= 0 and finite"; return 1; }
+  // erp and max_erv go into the right-hand side of every contact row; 0 is legal for both (no error reduction)
+  if (!is_finite(&c->erp)) { why = "erp must be finite"; return 1; }
+  if (!is_finite(&c->max_erv)) { why = "max_erv must be finite"; return 1; }
+  if (!(c->max_erv >= 0.0)) { why = "max_erv must be >= 0"; return 1; }
   if (t.gravity_rollouts < 0) { why = "gravity_rollouts must be >= 0"; return 1; }
   if (c->pgs_normal_iters < 0 || c->pgs_normal_iters > 10000) { why = "pgs_normal_iters out of range"; return 1; }
-  if (!(c->pgs_tol >= 0.0)) { why = "pgs_tol must be >= 0"; return 1; }
+  if (!is_finite(&c->pgs_tol) || !(c->pgs_tol >= 0.0)) { why = "pgs_tol must be >= 0 and finite"; return 1; }
   if (c->pgs_exact < 0 || c->pgs_exact > 10000) { why = "pgs_exact out of range"; return 1; }
   if (c->pgs_exact > 0 && c->dtype != OS2R_F64) { why = "pgs_exact (the exact finish of the contact solve) needs dtype f64"; return 1; }
   return 0;

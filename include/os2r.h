@@ -175,8 +175,8 @@ typedef struct Os2rConfig {
   int32_t pgs_normal_iters;/* preceding sweeps over normal + joint-friction rows that fix    */
                            /*   the tangential bounds (0: coupled pyramid)    */
   int32_t auto_reset;      /* SubprocVecEnv semantics (common/vec_env/subproc_vec_env.py:15) */
-  double erp;              /* contact error-reduction parameter                              */
-  double max_erv;          /* cap on the error-reduction velocity [m/s]                      */
+  double erp;              /* contact error-reduction parameter (finite; 0: none)            */
+  double max_erv;          /* cap on the error-reduction velocity [m/s] (finite, >= 0)       */
   double contact_margin;   /* candidates closer than this to the ground join the contact [m] */
   double pgs_tol;          /* an environment stops sweeping once a checked sweep moved no more     */
                            /*   energy than this [J]; 0: exact fixed points only                   */

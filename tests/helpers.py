@@ -48,6 +48,21 @@ def perturbed_model(mode, rng):
     return m
 
 
+def lying_states(model, n, rng):
+    """Fallen robots, for every chain of the reference (keyed by dof name): lying / crouching poses near the ground -- boom
+    pitch slightly negative (hip a few cm above / at the ground), leg folded, small velocities.  After a few env-steps nearly
+    every robot that can reach the ground carries contact rows.  -> (q, qd), [nq, n] each."""
+    import numpy as np
+    names = model["dof_names"]
+    nq = model["nq"]
+    q = np.zeros((nq, n)); qd = rng.normal(0, 0.5, (nq, n))
+    for name, (lo, hi) in (("planarizer_yaw_joint", (-0.3, 0.3)), ("planarizer_pitch_joint", (-0.05, 0.02)),
+                           ("boom_connector_joint", (-0.5, 0.5)), ("hip_joint", (0.8, 1.6)), ("knee_joint", (-2.8, -1.0))):
+        if name in names:
+            q[names.index(name)] = rng.uniform(lo, hi, n)
+    return q, qd
+
+
 def mixed_axis_chain(tmp_path):
     """A hand-made 3-dof chain with joint axes z, y, x and contact candidates on every body, and a raw-observation task for
     it: -> (model dict, task spec dict)."""
