@@ -535,6 +535,31 @@ int do_copy(Os2rSim* d, Os2rSim* s, const int32_t* index, int what, void* obs, h
   return OS2R_OK;
 }
 
+// os2r_linearize: one launch, grid.y over the columns the outputs asked for; the handle's arrays are only read
+template <typename T>
+int do_linearize(Os2rSim* s, const void* actions, const double* eps, void* next, void* jac_a, void* jac_b, hipStream_t st) {
+  LinArgs<T> p;
+  std::memset(&p, 0, sizeof(p));
+  p.s = make_args<T>(s);
+  p.s.actions = (const T*)actions;
+  // (a query: no violation is counted, the mirror and the work counters stay as they are)
+  p.s.violations = nullptr; p.s.mirror = nullptr; p.s.counters = nullptr; p.s.reason = nullptr; p.s.done_mask = nullptr;
+  p.eps_q = (T)eps[0]; p.eps_qd = (T)eps[1]; p.eps_a = (T)eps[2];
+  if (!(p.eps_q > T(0)) || !(p.eps_qd > T(0)) || !(p.eps_a > T(0))) { s->err = "os2r_linearize: eps must be positive in the handle's dtype (it rounds to zero)"; return OS2R_ERR_INVALID; }
+  if (!(p.eps_a < T(1))) { s->err = "os2r_linearize: eps[2] (action step) must be < 1 in the handle's dtype"; return OS2R_ERR_INVALID; }
+  p.next = (T*)next; p.jac_a = (T*)jac_a; p.jac_b = (T*)jac_b;
+  const int nq = s->nq;
+  if (jac_a) for (int j = 0; j < 2 * nq; ++j) p.col[p.ncols++] = j;
+  if (jac_b) for (int j = 0; j < 2; ++j) p.col[p.ncols++] = 2 * nq + j;
+  if (next) p.col[p.ncols++] = 2 * nq + 2;
+  if (Launcher<T>::linearize(nq, s->model_id, s->cfg.contact != 0, s->dr, p, st) != 0) {
+    s->err = "os2r_linearize: no kernel for this chain length";
+    return OS2R_ERR_INVALID;
+  }
+  HIP_TRY(s, hipGetLastError());
+  return OS2R_OK;
+}
+
 void free_all(Os2rSim* s) {
   for (void* p : s->allocs) (void)hipFree(p);
   s->allocs.clear();
@@ -737,6 +762,22 @@ int os2r_copy_envs(Os2rSim* dst, Os2rSim* src, const int32_t* index_dev, int32_t
   DeviceGuard guard(dst->cfg.device);
   return dst->cfg.dtype == OS2R_F64 ? do_copy<double>(dst, src, index_dev, what, obs_dev, (hipStream_t)stream)
                                     : do_copy<float>(dst, src, index_dev, what, obs_dev, (hipStream_t)stream);
+}
+
+int os2r_linearize(Os2rSim* sim, const void* actions_dev, const double eps[3], void* next_dev, void* a_dev, void* b_dev, void* stream) {
+  if (!sim) { g_create_error = "os2r_linearize: null handle"; return OS2R_ERR_INVALID; }
+  if (!actions_dev) { sim->err = "os2r_linearize: null actions"; return OS2R_ERR_INVALID; }
+  if (!eps) { sim->err = "os2r_linearize: null eps"; return OS2R_ERR_INVALID; }
+  if (!next_dev && !a_dev && !b_dev) { sim->err = "os2r_linearize: all three outputs are null"; return OS2R_ERR_INVALID; }
+  for (int k = 0; k < 3; ++k) {
+    // (bit pattern first: the library is built without NaN semantics, see validate)
+    if (!is_finite(&eps[k])) { sim->err = "os2r_linearize: eps must be finite"; return OS2R_ERR_INVALID; }
+    if (!(eps[k] > 0.0)) { sim->err = "os2r_linearize: eps must be positive"; return OS2R_ERR_INVALID; }
+  }
+  if (eps[2] >= 1.0) { sim->err = "os2r_linearize: eps[2] (action step) must be < 1"; return OS2R_ERR_INVALID; }
+  DeviceGuard guard(sim->cfg.device);
+  return sim->cfg.dtype == OS2R_F64 ? do_linearize<double>(sim, actions_dev, eps, next_dev, a_dev, b_dev, (hipStream_t)stream)
+                                    : do_linearize<float>(sim, actions_dev, eps, next_dev, a_dev, b_dev, (hipStream_t)stream);
 }
 
 int os2r_get_state(Os2rSim* sim, void* q_dev, void* qd_dev, void* stream) {

@@ -1023,6 +1023,173 @@ __global__ __launch_bounds__(kWave) void copy_envs_obs_kernel(const StepArgs<T> 
   store_obs_tile<T>(A.obs, obs, ts->obs_dim, e0, A.N, lane, tile);
 }
 
+// ----------------------------------------------------------------------------------------
+// os2r_linearize: finite-difference Jacobians of the transition x' = f(x, a) of one env-step
+// ----------------------------------------------------------------------------------------
+// One wave per (64 environments, column): grid.y walks the requested columns -- the 2 nq state columns of A, the two action
+// columns of B, the nominal point of `next` -- so that 64 environments of the 5-dof robot occupy 25 SIMDs, not one.  A wave
+// runs the physics of os2r_step (the same loads, bind_params, torques and substep instantiation as step_body) from the
+// column's upper point, stores f_hi into the column's output slots, runs it again from the lower point and replaces the slots
+// by (f_hi - f_lo) / (hi - lo): the same lane, the same addresses, program order, as the return of the policy epilogue.  Nothing
+// of width 2 nq lives across a physics loop, and nothing of the handle is written.
+constexpr int kLinMaxCols = 2 * OS2R_MAX_DOF + 3;
+// The argument begins with the StepArgs (as PolicyArgs does): bind_params and the loads take them as they are.
+template <typename T>
+struct LinArgs {
+  StepArgs<T> s;             // s.actions: the nominal actions [N][2]; nothing behind the handle's arrays is written
+  T eps_q, eps_qd, eps_a;
+  T* __restrict__ next;      // [2nq][N] or null
+  T* __restrict__ jac_a;     // [2nq][2nq][N] or null
+  T* __restrict__ jac_b;     // [2nq][2][N] or null
+  int ncols;                 // grid.y
+  int col[kLinMaxCols];      // column of wave row y: 0..nq-1 q_j, nq..2nq-1 qd_j, 2nq / 2nq+1 the actions, 2nq+2 the nominal point
+};
+
+template <typename T, typename MD, bool CONTACT, bool DR, bool STD_SWEEPS, int SOLVER>
+__device__ __forceinline__ void linearize_body(const LinArgs<T>& P) {
+  const StepArgs<T>& A = P.s;
+  constexpr int NQ = MD::NQ;
+  constexpr bool kCandInLds = CONTACT && MD::CMASK != 0u && !MD::kStatic;
+  constexpr int kParamWords = DR ? 4 * NQ * kWave : 0;
+  __shared__ T tile[lds_words<NQ>() + kParamWords + (kCandInLds ? kCandWords : 0)];
+  const int lane = threadIdx.x;
+  const long long e0 = (long long)blockIdx.x * kWave;
+  const bool valid = e0 + lane < A.N;
+  const long long e_lane = valid ? e0 + lane : A.N - 1;  // tail lanes shadow the last env, stores are masked
+  const MD md = make_model<T, MD>(A);
+  T* cand_lds = tile + lds_words<NQ>() + kParamWords;
+  if constexpr (kCandInLds) {
+    const int nc3 = 3 * md.cand_begin(NQ);
+    for (int k = lane; k < nc3; k += kWave) cand_lds[k] = md.cand(k / 3, k % 3);
+    __syncthreads();
+  }
+  const int col = P.col[blockIdx.y];   // wave-uniform
+  const int npass = col == 2 * NQ + 2 ? 1 : 2;
+  T sn[NQ], cs[NQ];
+  WorkCounts wc;
+#ifdef OS2R_STAMPS
+  unsigned long long stamps[kStamps] = {}, stamp_prev = 0;   // (the diagnostic build's substep takes them; nothing reads these)
+#endif
+#pragma nounroll
+  for (int pass = 0; pass < npass; ++pass) {
+    // (as in a rollout: the environment index is a fresh value in every pass, so that no address is held across the physics loop)
+    long long e = e_lane;
+    asm volatile("" : "+v"(e));
+    T q[NQ], qd[NQ];
+#pragma unroll
+    for (int i = 0; i < NQ; ++i) {
+      q[i] = A.q[i * A.N + e];
+      qd[i] = A.qd[i * A.N + e];
+    }
+    Params<T, MD, DR> par;
+    bind_params<T, MD, DR>(A, e, md, par, tile + lds_words<NQ>() + lane);
+    constexpr bool kCarry = sizeof(T) == 8 && SOLVER != kSolverSweeps;
+    SolverCarry<T, NQ> carry;
+    if constexpr (kCarry) {
+      carry.act = A.solver_flags[e];
+#pragma unroll
+      for (int b = 0; b < NQ; ++b) {
+        if (CONTACT && ((MD::CMASK >> b) & 1u)) {
+          carry.ln[b] = A.solver_l[(0 * NQ + b) * A.N + e];
+          carry.lx[b] = A.solver_l[(1 * NQ + b) * A.N + e];
+          carry.ly[b] = A.solver_l[(2 * NQ + b) * A.N + e];
+        }
+        carry.lf[b] = A.solver_l[(3 * NQ + b) * A.N + e];
+      }
+    }
+    T ax = A.actions[2 * e], ay = A.actions[2 * e + 1];
+    ax = ax < T(-1) ? T(-1) : (ax > T(1) ? T(1) : ax);   // a query: clamped silently, no violation counted
+    ay = ay < T(-1) ? T(-1) : (ay > T(1) ? T(1) : ay);
+    // the column's point: x_j + h, then x_j - h (one rounded add each); an action stops at its limit
+    if (npass == 2) {
+#pragma clang fp contract(off)
+      const T sign = pass == 0 ? T(1) : T(-1);
+      const T hq = sign * P.eps_q, hv = sign * P.eps_qd, ha = sign * P.eps_a;
+#pragma unroll
+      for (int i = 0; i < NQ; ++i) {
+        q[i] = opaque(col == i ? q[i] + hq : q[i]);
+        qd[i] = opaque(col == NQ + i ? qd[i] + hv : qd[i]);
+      }
+      T px = ax + ha, py = ay + ha;
+      px = px < T(-1) ? T(-1) : (px > T(1) ? T(1) : px);
+      py = py < T(-1) ? T(-1) : (py > T(1) ? T(1) : py);
+      ax = opaque(col == 2 * NQ ? px : ax);
+      ay = opaque(col == 2 * NQ + 1 ? py : ay);
+    }
+    T tau_hip, tau_knee;
+    {
+#pragma clang fp contract(off)
+      tau_hip = md.max_torque(0) * ax;
+      tau_knee = md.max_torque(1) * ay;
+    }
+    for (int s = 0; s < A.substeps; ++s) {
+      substep<T, MD, CONTACT, DR, false, SOLVER>(
+          md, par, q, qd, sn, cs, s == 0, tau_hip, tau_knee, A.dt, A.erp, A.max_erv, A.margin,
+          STD_SWEEPS ? std_iters<T>(NQ) : A.pgs_iters, STD_SWEEPS ? StdSolver<T>::kNormalIters : A.pgs_normal_iters,
+          A.pgs_exact, A.pgs_tol, tile, cand_lds, as_const(A.model), wc, carry
+#ifdef OS2R_STAMPS
+          , stamps, stamp_prev
+#endif
+      );
+    }
+    __syncthreads();
+    // behind the physics loop: a fresh environment index and the arguments re-read from the argument segment (step_body)
+    long long ep = e;
+    asm volatile("" : "+v"(ep));
+    const OS2R_CONST LinArgs<T>* args_e = (const OS2R_CONST LinArgs<T>*)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(args_e));
+    const LinArgs<T>& Pe = *(const LinArgs<T>*)args_e;
+    const long long N = Pe.s.N;
+    // the column's slots: element [i][j] of an [2nq][width][N] array
+    T* out = Pe.jac_a;
+    int width = 2 * NQ, j = col;
+    if (col >= 2 * NQ) { out = Pe.jac_b; width = 2; j = col - 2 * NQ; }
+    if (col == 2 * NQ + 2) { out = Pe.next; width = 1; j = 0; }
+    if (valid) {
+#pragma clang fp contract(off)
+      if (pass == 0) {   // f_hi waits in the output slots; the nominal point is the output
+#pragma unroll
+        for (int i = 0; i < NQ; ++i) {
+          out[(long long)(i * width + j) * N + ep] = q[i];
+          out[(long long)((NQ + i) * width + j) * N + ep] = qd[i];
+        }
+      } else {
+        // hi - lo of the column, from the stored value again: the same two rounded adds
+        T hi, lo;
+        if (col < 2 * NQ) {
+          const T x = col < NQ ? Pe.s.q[(long long)col * N + ep] : Pe.s.qd[(long long)(col - NQ) * N + ep];
+          const T h = col < NQ ? Pe.eps_q : Pe.eps_qd;
+          hi = x + h;
+          lo = x - h;
+        } else {
+          T a = Pe.s.actions[2 * ep + j];
+          a = a < T(-1) ? T(-1) : (a > T(1) ? T(1) : a);
+          hi = a + Pe.eps_a;
+          hi = hi > T(1) ? T(1) : hi;
+          lo = a - Pe.eps_a;
+          lo = lo < T(-1) ? T(-1) : lo;
+        }
+        const T den = opaque(hi) - opaque(lo);
+        // one rounded subtraction, one IEEE division: none of the reciprocal estimates of the physics code
+#pragma unroll
+        for (int i = 0; i < NQ; ++i) {
+          const long long at_q = (long long)(i * width + j) * N + ep, at_v = (long long)((NQ + i) * width + j) * N + ep;
+          const T fq = out[at_q], fv = out[at_v];
+          out[at_q] = (fq - opaque(q[i])) / den;
+          out[at_v] = (fv - opaque(qd[i])) / den;
+        }
+      }
+    }
+    // the second pass reads what this one stored: vector memory operations of a wave are performed in order
+    asm volatile("" ::: "memory");
+  }
+}
+
+template <typename T, typename MD, bool CONTACT, bool DR, bool STD_SWEEPS, int SOLVER>
+__global__ OS2R_STEP_KERNEL_ATTRS(T) void linearize_kernel(const LinArgs<T> P) {
+  linearize_body<T, MD, CONTACT, DR, STD_SWEEPS, SOLVER>(P);
+}
+
 // launch tables (defined in the per-dtype instantiation units)
 template <typename T>
 struct Launcher {
@@ -1039,6 +1206,8 @@ struct Launcher {
   // os2r_copy_envs: the copy itself, and the observation of the stored state into args.obs
   static void copy_envs(const CopyArgs<T>& args, hipStream_t s);
   static int copy_obs(int nq, const StepArgs<T>& args, hipStream_t s);
+  // os2r_linearize: the variant whose substep instantiation is the one Launcher::step runs for this handle
+  static int linearize(int nq, int model_id, bool contact, bool dr, const LinArgs<T>& args, hipStream_t s);
 };
 
 }  // namespace os2r

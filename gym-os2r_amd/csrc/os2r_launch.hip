@@ -12,6 +12,10 @@ int policy_rollout_unit(bool contact, bool dr, const PolicyArgs<R>& a, hipStream
 template <typename R, int N_>
 int policy_unit(const PolicyArgs<R>& a, hipStream_t s);
 
+template <typename R, int UNIT>
+int linearize_unit(bool contact, bool dr, const LinArgs<R>& a, hipStream_t s);
+
+#define OS2R_DECL_LIN(R, U) template <> int linearize_unit<R, U>(bool, bool, const LinArgs<R>&, hipStream_t);
 #define OS2R_DECL_STEP(R, U) template <> int step_unit<R, U>(bool, bool, const StepArgs<R>&, hipStream_t);
 #define OS2R_DECL_RESET(R, N_) template <> int reset_unit<R, N_>(bool, const StepArgs<R>&, hipStream_t);
 #define OS2R_DECL_PROLL(R, U) template <> int policy_rollout_unit<R, U>(bool, bool, const PolicyArgs<R>&, hipStream_t);
@@ -21,7 +25,9 @@ int policy_unit(const PolicyArgs<R>& a, hipStream_t s);
   OS2R_DECL_STEP(R, 12) OS2R_DECL_STEP(R, 13) OS2R_DECL_STEP(R, 14) OS2R_DECL_STEP(R, 15)           \
   OS2R_DECL_RESET(R, 2) OS2R_DECL_RESET(R, 3) OS2R_DECL_RESET(R, 4) OS2R_DECL_RESET(R, 5)           \
   OS2R_DECL_PROLL(R, 0) OS2R_DECL_PROLL(R, 1) OS2R_DECL_PROLL(R, 2) OS2R_DECL_PROLL(R, 3)           \
-  OS2R_DECL_POLICY(R, 2) OS2R_DECL_POLICY(R, 3) OS2R_DECL_POLICY(R, 4) OS2R_DECL_POLICY(R, 5)
+  OS2R_DECL_POLICY(R, 2) OS2R_DECL_POLICY(R, 3) OS2R_DECL_POLICY(R, 4) OS2R_DECL_POLICY(R, 5)       \
+  OS2R_DECL_LIN(R, 0) OS2R_DECL_LIN(R, 1) OS2R_DECL_LIN(R, 2) OS2R_DECL_LIN(R, 3)                   \
+  OS2R_DECL_LIN(R, 12) OS2R_DECL_LIN(R, 13) OS2R_DECL_LIN(R, 14) OS2R_DECL_LIN(R, 15)
 OS2R_DECL(float)
 OS2R_DECL(double)
 
@@ -91,6 +97,24 @@ int Launcher<T>::copy_obs(int nq, const StepArgs<T>& a, hipStream_t s) {
     case 3: hipLaunchKernelGGL((copy_envs_obs_kernel<T, 3>), grid, block, 0, s, a); return 0;
     case 4: hipLaunchKernelGGL((copy_envs_obs_kernel<T, 4>), grid, block, 0, s, a); return 0;
     case 5: hipLaunchKernelGGL((copy_envs_obs_kernel<T, 5>), grid, block, 0, s, a); return 0;
+    default: return 1;
+  }
+}
+// os2r_linearize: the same choice of unit as Launcher::step
+template <typename T>
+int Launcher<T>::linearize(int nq, int model_id, bool contact, bool dr, const LinArgs<T>& a, hipStream_t s) {
+  switch (model_id) {
+    case 0: return linearize_unit<T, 0>(contact, dr, a, s);
+    case 1: return linearize_unit<T, 1>(contact, dr, a, s);
+    case 2: return linearize_unit<T, 2>(contact, dr, a, s);
+    case 3: return linearize_unit<T, 3>(contact, dr, a, s);
+    default: break;
+  }
+  switch (nq) {
+    case 2: return linearize_unit<T, 12>(contact, dr, a, s);
+    case 3: return linearize_unit<T, 13>(contact, dr, a, s);
+    case 4: return linearize_unit<T, 14>(contact, dr, a, s);
+    case 5: return linearize_unit<T, 15>(contact, dr, a, s);
     default: return 1;
   }
 }

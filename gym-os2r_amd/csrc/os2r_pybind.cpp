@@ -43,6 +43,9 @@ PYBIND11_MODULE(_os2r_py, m) {
                                      P(term), (uint16_t*)P(why), P(act), P(eps), P(st)); }, nogil);
   m.def("copy_envs", [](addr dst, addr src, addr index, int what, addr obs, addr st) {
     return os2r_copy_envs(H(dst), H(src), (const int32_t*)P(index), what, P(obs), P(st)); }, nogil);
+  m.def("linearize", [](addr h, addr act, double eq, double ev, double ea, addr next, addr ja, addr jb, addr st) {
+    const double eps[3] = {eq, ev, ea};
+    return os2r_linearize(H(h), P(act), eps, P(next), P(ja), P(jb), P(st)); }, nogil);
   m.def("get_solver_state", [](addr h, addr l, addr f, addr st) { return os2r_get_solver_state(H(h), P(l), (uint32_t*)P(f), P(st)); }, nogil);
   m.def("set_solver_state", [](addr h, addr l, addr f, addr st) { return os2r_set_solver_state(H(h), P(l), (const uint32_t*)P(f), P(st)); }, nogil);
   m.def("get_state", [](addr h, addr q, addr qd, addr st) { return os2r_get_state(H(h), P(q), P(qd), P(st)); }, nogil);

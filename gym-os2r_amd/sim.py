@@ -76,6 +76,10 @@ class _PybindLib:
     def os2r_copy_envs(self, dst, src, index, what, obs, st):
         return self.m.copy_envs(self._a(dst), self._a(src), self._a(index), int(what), self._a(obs), self._a(st))
 
+    def os2r_linearize(self, h, act, eps, nxt, ja, jb, st):
+        return self.m.linearize(self._a(h), self._a(act), float(eps[0]), float(eps[1]), float(eps[2]), self._a(nxt), self._a(ja),
+                                self._a(jb), self._a(st))
+
     def os2r_get_action_history(self, h, w, o, st):
         return self.m.get_action_history(self._a(h), int(w), self._a(o), self._a(st))
 
@@ -518,6 +522,70 @@ class HipSim:
         obs = self._new(self.N, self.D) if want_obs else None
         self._check(self._lib.os2r_copy_envs(self._h, src._h, _ptr(index), what, _ptr(obs), self._stream()), "os2r_copy_envs")
         return obs
+
+    # -- linearisation ---------------------------------------------------------------------
+    def _linearize_eps(self, eps):
+        """eps of linearize() -> (eps_q, eps_qd, eps_a) as Python floats, checked."""
+        import math
+        if eps is None:
+            # the textbook central-difference step (cube root of the machine epsilon) for all three: a starting point, not tuned
+            # to the robot, the time step or the contact state
+            eps = float(torch.finfo(self.dtype).eps) ** (1.0 / 3.0)
+        if isinstance(eps, bool):
+            raise ValueError("linearize: eps must be a float or a sequence of three floats")
+        if isinstance(eps, (int, float)):
+            eps = (eps, eps, eps)
+        try:
+            eps = tuple(float(v) for v in eps)
+        except (TypeError, ValueError):
+            raise ValueError(f"linearize: eps must be a float or a sequence of three floats, got {type(eps)}") from None
+        if len(eps) != 3:
+            raise ValueError(f"linearize: eps must hold three values (eps_q, eps_qd, eps_a), got {len(eps)}")
+        if not all(math.isfinite(v) and v > 0.0 for v in eps):
+            raise ValueError(f"linearize: every eps must be finite and > 0, got {eps}")
+        if eps[2] >= 1.0:
+            raise ValueError(f"linearize: eps_a (the action step) must be < 1, got {eps[2]}")
+        return eps
+
+    def linearize_into(self, actions, eps=None, next_out=None, A_out=None, B_out=None):
+        """Allocation-free variant of linearize() writing into caller tensors in the kernel's layout (include/os2r.h:
+        os2r_linearize): actions [N, 2], next_out [2nq, N], A_out [2nq, 2nq, N], B_out [2nq, 2, N], the environment index
+        fastest; each output may be None, not all three.  Shapes, dtypes, device and contiguity are checked before the library
+        is called (it takes addresses)."""
+        n2 = 2 * self.nq
+        eps = self._linearize_eps(eps)
+        if actions is None:
+            raise ValueError("linearize: actions are required")
+        if next_out is None and A_out is None and B_out is None:
+            raise ValueError("linearize: nothing asked for (next, A and B are all off)")
+        self._out(actions, (self.N, 2), self.dtype, "linearize: actions")
+        self._out(next_out, (n2, self.N), self.dtype, "linearize: next_out")
+        self._out(A_out, (n2, n2, self.N), self.dtype, "linearize: A_out")
+        self._out(B_out, (n2, 2, self.N), self.dtype, "linearize: B_out")
+        self._check(self._lib.os2r_linearize(self._h, _ptr(actions), (C.c_double * 3)(*eps), _ptr(next_out), _ptr(A_out), _ptr(B_out),
+                                             self._stream()), "os2r_linearize")
+
+    def linearize(self, actions, eps=None, want_next: bool = True, want_A: bool = True, want_B: bool = True):
+        """Finite-difference Jacobians of one env-step about every environment's stored state and `actions` [N, 2], in one
+        launch (include/os2r.h: os2r_linearize).  With x = (q, qd) and x' = f(x, a) what step(actions) would leave in
+        get_state() (no observation, reward, done or reset; actions clamped to [-1, 1] silently):
+        -> (next_q [nq, N], next_qd [nq, N], A [N, 2nq, 2nq] = dx'/dx, B [N, 2nq, 2] = dx'/da), None where not wanted.
+        The handle is not advanced or changed in any way.  A and B are permuted views of the kernel's [2nq][.][N] layout: they
+        are NOT contiguous (call .contiguous() before handing them to code that needs it); next_q / next_qd are the two halves
+        of one [2nq, N] tensor.  eps: a float, or (eps_q [rad], eps_qd [rad/s], eps_a [action units]); central differences,
+        one-sided at a torque limit.  The default, torch.finfo(dtype).eps ** (1/3) for all three, is the textbook
+        central-difference step and is not tuned: across a change of contact mode the quotient is a secant, whatever eps."""
+        n2 = 2 * self.nq
+        eps = self._linearize_eps(eps)
+        if not (want_next or want_A or want_B):
+            raise ValueError("linearize: nothing asked for (next, A and B are all off)")
+        a = self._in(actions, (self.N, 2))
+        nxt = self._new(n2, self.N) if want_next else None
+        ja = self._new(n2, n2, self.N) if want_A else None
+        jb = self._new(n2, 2, self.N) if want_B else None
+        self.linearize_into(a, eps, nxt, ja, jb)
+        return (nxt[:self.nq] if want_next else None, nxt[self.nq:] if want_next else None,
+                ja.permute(2, 0, 1) if want_A else None, jb.permute(2, 0, 1) if want_B else None)
 
     def action_violations_into(self, dst: torch.Tensor, clear: bool = True):
         """Copy the running count of out-of-range caller actions into ``dst`` (one int32/uint32 element,

@@ -41,7 +41,8 @@ extern "C" {
 
 #define OS2R_ABI_VERSION 6   /* os2r_create also takes configs stamped 5 (Os2rConfig did not change in 6) */
 #define OS2R_ABI_MINOR 1     /* entry points added within ABI 6 (os2r_abi_minor): 1: os2r_rollout_policy_noisy */
-/* os2r_copy_envs was added later without a new minor: a binding finds out whether it is there by looking the symbol up */
+/* os2r_copy_envs and, after it, os2r_linearize were added later without a new minor: a binding finds out whether they are
+ * there by looking the symbol up */
 
 #define OS2R_MAX_DOF 5      /* yaw, pitch, boom_connector, hip, knee                       */
 #define OS2R_MAX_CAND 192   /* ground-contact candidate points of one model                */
@@ -394,6 +395,37 @@ OS2R_API int os2r_set_episode_info(Os2rSim* sim, const int32_t* steps_dev, const
 #define OS2R_COPY_STATE 1   /* q, qd, action history 0 and 1, solver impulses and flags, elapsed steps, episode index, pose id */
 #define OS2R_COPY_PARAMS 2  /* mass_scale, damping, friction, mu, gravity */
 OS2R_API int os2r_copy_envs(Os2rSim* dst, Os2rSim* src, const int32_t* index_dev, int32_t what, void* obs_dev, void* stream);
+
+/* Finite-difference Jacobians of one env-step, in one launch.  For every environment e let x = (q_0 .. q_{nq-1},
+ * qd_0 .. qd_{nq-1}) be the stored state and a = actions_dev[e] ([num_envs][2], the handle's dtype), clamped to [-1, 1]
+ * silently: this is a query and counts no violation.  The transition f(x, a) is the (q, qd) an os2r_step with that action
+ * leaves after its `substeps` physics iterations, started from the environment's own solver state and parameters: no
+ * observation, reward, done or reset (as on a handle with auto_reset = 0).
+ *   eps        {eps_q [rad], eps_qd [rad/s], eps_a [action units]}, host memory, read before the call returns; each finite
+ *              and > 0 (also after rounding to the handle's dtype), eps[2] < 1
+ *   Points, all in the handle's dtype: state column j is evaluated at x_j + h and x_j - h (one rounded add each; h = eps[0]
+ *   for a q column, eps[1] for a qd column); action column j at min(a_j + eps[2], 1) and max(a_j - eps[2], -1), so the quotient
+ *   turns one-sided at a torque limit on its own.  Column j of A or B is (f(hi) - f(lo)) / (hi - lo): one rounded subtraction
+ *   above, one below, one IEEE division -- in fp32 too.
+ *   next_dev   nullable, [2nq][N]: f(x, a), the q' rows first, then the qd' rows
+ *   a_dev      nullable, [2nq][2nq][N]: element [i][j] = d x'_i / d x_j
+ *   b_dev      nullable, [2nq][2][N]:   element [i][j] = d x'_i / d a_j
+ * All three are struct-of-arrays with the environment index fastest; at least one is required, and the evaluations of a null
+ * output are not run.  The columns are independent waves: 64 environments of the 5-dof robot fill 25 SIMDs.
+ * The handle is only read: state, solver state, histories, parameters, episode and step counters, the violation count and
+ * its mirror, the done-reason / done-mask buffers and the work counters are as they were.  Stream-ordered on `stream`, no
+ * host synchronisation, no allocation, no buffer of the handle's.
+ * Contract: every f(.) above equals, bit for bit, what os2r_step leaves in os2r_get_state when started from that point, the
+ * same solver state, the same parameters and that action, for every configuration os2r_create accepts.  Exception: for a
+ * robot that runs a registered code object (os2r_register_model_kernels) this call uses the generic run-time-model kernels
+ * of the library; the equality then holds against those (a handle created without the registration, OS2R_JIT=0 in the
+ * Python package), not against the robot's own code object, which exports no linearise kernel.
+ * A quotient whose two evaluations end in different contact modes is the secant across the kink: eps is the caller's tool,
+ * the library does not judge it.
+ * Errors: OS2R_ERR_INVALID for a null handle (os2r_last_error(NULL)), null actions_dev, null eps, all outputs null, an eps
+ * that is not finite or not > 0, or eps[2] >= 1; os2r_last_error names the cause.                                          */
+OS2R_API int os2r_linearize(Os2rSim* sim, const void* actions_dev, const double eps[3], void* next_dev, void* a_dev, void* b_dev,
+                            void* stream);
 
 /* Global step counter that keys the on-device action RNG. */
 OS2R_API int os2r_get_step_count(Os2rSim* sim, uint64_t* out);
