@@ -36,6 +36,9 @@ POLICY_PER_ENV, POLICY_TANH, POLICY_FIRST_EPISODE = 1, 2, 4
 # os2r_rollout_policy_noisy only: sigma per environment ([2][N]); the random stream of its noise
 POLICY_SIGMA_PER_ENV = 8
 STREAM_POLICY_NOISE = 5
+# os2r_rollout_policy_scheduled only: the slot comes from the environment's episode steps (else the window's step index); the
+# schedule wraps (else its last slot is held)
+POLICY_CLOCK_EPISODE, POLICY_SCHEDULE_WRAP = 16, 32
 # os2r_copy_envs: which arrays of an environment move (include/os2r.h)
 COPY_STATE, COPY_PARAMS = 1, 2
 

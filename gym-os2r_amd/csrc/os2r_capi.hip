@@ -421,13 +421,15 @@ int dev_alloc(Os2rSim* s, void** p, size_t bytes) {
 template <typename T>
 int do_rollout_policy(Os2rSim* s, int K, const void* w, int flags, void* ret, int32_t* len, void* obs, void* reward, uint8_t* done,
                       void* term, uint16_t* reason, hipStream_t st, const void* sigma = nullptr, uint32_t salt = 0u,
-                      void* act_out = nullptr, void* eps_out = nullptr) {
+                      void* act_out = nullptr, void* eps_out = nullptr, int period = 0, int first_slot = 0) {
   const size_t N = (size_t)s->cfg.num_envs, D = (size_t)s->D;
   PolicyArgs<T> p;
   std::memset(&p, 0, sizeof(p));
   p.w = (const T*)w; p.flags = flags; p.ret = (T*)ret; p.len = len;
   // exploration noise (os2r_rollout_policy_noisy): a null sigma is the deterministic policy
   p.sigma = (const T*)sigma; p.salt = salt; p.act_out = (T*)act_out; p.eps_out = (T*)eps_out;
+  // time schedule (os2r_rollout_policy_scheduled): period 0 is the one set of the two entry points above
+  p.period = period; p.first_slot = first_slot;
   if (!s->jit && !s->counters) {
     p.s = make_args<T>(s);
     p.s.obs = (T*)obs; p.s.reward = (T*)reward; p.s.done = done; p.s.term_obs = (T*)term; p.s.reason = reason;
@@ -452,6 +454,11 @@ int do_rollout_policy(Os2rSim* s, int K, const void* w, int flags, void* ret, in
     p.s = make_args<T>(s);   // (with it the step counter of env-step k, which keys the noise)
     p.act_out = act_out ? (T*)act_out + (size_t)k * N * 2 : nullptr;
     p.eps_out = eps_out ? (T*)eps_out + (size_t)k * N * 2 : nullptr;
+    if (period > 0 && !(flags & OS2R_POLICY_CLOCK_EPISODE)) {
+      // the window clock of env-step k, reduced to its slot here (the sum may not fit 32 bits); the kernel's rule leaves a slot as it is
+      const long long t = (long long)first_slot + k;
+      p.first_slot = (int)((flags & OS2R_POLICY_SCHEDULE_WRAP) ? t % period : (t < period - 1 ? t : period - 1));
+    }
     if (Launcher<T>::policy(s->nq, p, st) != 0) { s->err = "no policy kernel for this chain length"; rc = OS2R_ERR_INVALID; break; }
     // the sums need the step's reward and done flag: the handle's scratch outputs stand in for the ones not asked for
     T* const rew_k = reward ? (T*)reward + (size_t)k * N : (T*)s->b_rew;
@@ -743,6 +750,31 @@ int os2r_rollout_policy_noisy(Os2rSim* sim, int nsteps, const void* weights_dev,
                                          reason_dev, st, sigma_dev, salt, action_dev, noise_dev)
              : do_rollout_policy<float>(sim, nsteps, weights_dev, flags, return_dev, length_dev, obs_dev, reward_dev, done_dev, term_obs_dev,
                                         reason_dev, st, sigma_dev, salt, action_dev, noise_dev);
+}
+
+int os2r_rollout_policy_scheduled(Os2rSim* sim, int nsteps, const void* weights_dev, int32_t period, int32_t first_slot, int32_t flags,
+                                  const void* sigma_dev, uint32_t salt, void* return_dev, int32_t* length_dev, void* obs_dev,
+                                  void* reward_dev, uint8_t* done_dev, void* term_obs_dev, uint16_t* reason_dev, void* action_dev,
+                                  void* noise_dev, void* stream) {
+  if (!sim) { g_create_error = "os2r_rollout_policy_scheduled: null handle"; return OS2R_ERR_INVALID; }
+  if (nsteps < 1) { sim->err = "os2r_rollout_policy_scheduled: nsteps must be >= 1"; return OS2R_ERR_INVALID; }
+  if (period < 1) { sim->err = "os2r_rollout_policy_scheduled: period must be >= 1"; return OS2R_ERR_INVALID; }
+  if (first_slot < 0) { sim->err = "os2r_rollout_policy_scheduled: first_slot must be >= 0"; return OS2R_ERR_INVALID; }
+  if (!weights_dev) { sim->err = "os2r_rollout_policy_scheduled: null weights"; return OS2R_ERR_INVALID; }
+  if (flags & ~(OS2R_POLICY_PER_ENV | OS2R_POLICY_TANH | OS2R_POLICY_FIRST_EPISODE | OS2R_POLICY_SIGMA_PER_ENV |
+                OS2R_POLICY_CLOCK_EPISODE | OS2R_POLICY_SCHEDULE_WRAP)) {
+    sim->err = "os2r_rollout_policy_scheduled: unknown flag bits";
+    return OS2R_ERR_INVALID;
+  }
+  if (!sigma_dev && noise_dev) { sim->err = "os2r_rollout_policy_scheduled: noise_dev needs sigma_dev"; return OS2R_ERR_INVALID; }
+  if (!sigma_dev && salt != 0u) { sim->err = "os2r_rollout_policy_scheduled: a non-zero salt needs sigma_dev"; return OS2R_ERR_INVALID; }
+  DeviceGuard guard(sim->cfg.device);
+  hipStream_t st = (hipStream_t)stream;
+  return sim->cfg.dtype == OS2R_F64
+             ? do_rollout_policy<double>(sim, nsteps, weights_dev, flags, return_dev, length_dev, obs_dev, reward_dev, done_dev, term_obs_dev,
+                                         reason_dev, st, sigma_dev, salt, action_dev, noise_dev, period, first_slot)
+             : do_rollout_policy<float>(sim, nsteps, weights_dev, flags, return_dev, length_dev, obs_dev, reward_dev, done_dev, term_obs_dev,
+                                        reason_dev, st, sigma_dev, salt, action_dev, noise_dev, period, first_slot);
 }
 
 int os2r_copy_envs(Os2rSim* dst, Os2rSim* src, const int32_t* index_dev, int32_t what, void* obs_dev, void* stream) {

@@ -401,11 +401,15 @@ struct PolicyArgs {
   T* __restrict__ act_out;       // nullable: applied actions, [K][N][2] (fused) / step k's [N][2] slice (launch loop)
   T* __restrict__ eps_out;       // nullable: the noise eps, same shape
   uint32_t salt;                 // enters the noise counter: c1 = (c >> 32) ^ salt
+  // os2r_rollout_policy_scheduled (appended likewise)
+  int period;                    // 0: no schedule, w is one set; T >= 1: w is [T] sets, one per slot
+  int first_slot;                // the clock's offset: the fused kernel adds its step index k, the launch loop's host has added it
 };
 
 // The one policy function of both paths (fused rollout, launch loop).  Evaluation order is part of the contract
 // (include/os2r.h): z_j = (((b_j + W_j0*o_0) + W_j1*o_1) + ...), each product rounded on its own.  Shared weights are
-// wave-uniform (scalar loads); per-env ones are [2(D+1)][N] and load coalesced.
+// wave-uniform: one scalar base, every lane the same address (the compiler issues 16-byte vector loads off that base, all of
+// them ahead of the first product); per-env ones are [2(D+1)][N] and load coalesced.
 template <typename T>
 __device__ __forceinline__ void policy_presquash(const T* __restrict__ w, int flags, int D, long long N, long long e,
                                                  const T (&obs)[OS2R_MAX_OBS], T (&z)[2]) {
@@ -464,14 +468,47 @@ __device__ __forceinline__ void policy_noise(const T* __restrict__ sigma, int fl
   }
 }
 
-// a = squash(z + sigma * eps) of environment e (lane `valid`: not a shadow lane of a tail wave) in the env-step with counter c;
-// with P.sigma the action and the noise go to act_out / eps_out + 2 * at (nullable).  The branch on P.sigma is wave-uniform.
+// The slot of a time-scheduled policy (os2r_rollout_policy_scheduled): t >= 0 is held at period - 1, or wraps.  t < 2^32, period
+// < 2^31: the remainder is taken of each 32-bit summand on its own (a 64-bit remainder is a hundred instructions).
+__device__ __forceinline__ long long policy_slot(int flags, int period, unsigned first, unsigned dt) {
+  const unsigned per = (unsigned)period;
+  if (flags & OS2R_POLICY_SCHEDULE_WRAP) {
+    const unsigned s = first % per + dt % per;   // < 2 * per: no carry
+    return (long long)(s >= per ? s - per : s);
+  }
+  const long long t = (long long)first + (long long)dt;
+  return t < (long long)per - 1 ? t : (long long)per - 1;
+}
+
+// a = squash(z + sigma * eps) of environment e (lane `valid`: not a shadow lane of a tail wave) in the env-step with counter c,
+// the k-th of the fused window (launch loop: 0); the action and, with P.sigma, the noise go to act_out / eps_out + 2 * at
+// (nullable).  The branches on P.sigma, P.period and the clock flag are wave-uniform: they test kernel arguments.
+// With a schedule (P.period > 0) the weights are those of the environment's slot, [period] sets in the layout of one:
+//   window clock   slot of first_slot + k, the same for every lane: scalar arithmetic on the base, after which the shared set's
+//                  loads are the wave-uniform ones of the one-set path and the per-env ones coalesced
+//   episode clock  slot of first_slot + steps[e] (one 4-byte load by the lane; a negative count is taken as 0): a base per lane.
+//                  The shared table is gathered -- 2(D+1) independent loads from [period][2][D+1], issued together ahead of the
+//                  first product --; per-env, every lane reads its own column at its own slot
 template <typename T>
 __device__ __forceinline__ void policy_action(const PolicyArgs<T>* P, const StepArgs<T>& A, int D, long long e, bool valid,
-                                              unsigned long long c, long long at, const T (&obs)[OS2R_MAX_OBS], T& ax, T& ay) {
+                                              unsigned long long c, int k, long long at, const T (&obs)[OS2R_MAX_OBS], T& ax,
+                                              T& ay) {
   const int flags = P->flags;
   T z[2];
-  policy_presquash<T>(P->w, flags, D, A.N, e, obs, z);
+  if (P->period == 0) {
+    policy_presquash<T>(P->w, flags, D, A.N, e, obs, z);
+  } else {
+    // elements between two slots
+    const long long stride = (long long)(2 * (D + 1)) * ((flags & OS2R_POLICY_PER_ENV) ? A.N : 1ll);
+    if (flags & OS2R_POLICY_CLOCK_EPISODE) {
+      const int st = A.steps[e];
+      const long long slot = policy_slot(flags, P->period, (unsigned)P->first_slot, (unsigned)(st < 0 ? 0 : st));
+      policy_presquash<T>(P->w + slot * stride, flags, D, A.N, e, obs, z);
+    } else {
+      const long long slot = policy_slot(flags, P->period, (unsigned)P->first_slot, (unsigned)k);
+      policy_presquash<T>(P->w + slot * stride, flags, D, A.N, e, obs, z);
+    }
+  }
   if (P->sigma) {
     T eps[2];
     policy_noise<T>(P->sigma, flags, A.N, e, A.seed, (uint32_t)(A.env_offset + e), c, P->salt, z, eps);
@@ -482,6 +519,7 @@ __device__ __forceinline__ void policy_action(const PolicyArgs<T>* P, const Step
     }
   } else {
     policy_squash<T>(flags, z);
+    if (valid && P->act_out) { P->act_out[2 * at] = z[0]; P->act_out[2 * at + 1] = z[1]; }
   }
   ax = z[0];
   ay = z[1];
@@ -618,7 +656,7 @@ __device__ __forceinline__ void step_body(const StepArgs<T>& A) {
       unsigned why0;
       observe<T, NQ, LAY>(ts, q, qd, h2x, h2y, o, dn0, why0);
       // (with sigma: the noise is drawn and a, eps of step k are stored here by the owning lane: nothing of it lives on)
-      policy_action<T>(pa, A, D, e, valid, step_count, ko + e, o, ax, ay);
+      policy_action<T>(pa, A, D, e, valid, step_count, k, ko + e, o, ax, ay);
     } else if (A.actions) {
       ax = A.actions[2 * (ko + e)];
       ay = A.actions[2 * (ko + e) + 1];
@@ -846,7 +884,7 @@ __global__ __launch_bounds__(kWave) void policy_kernel(const PolicyArgs<T> P) {
   unsigned why;
   observe<T, NQ>(ts, q, qd, h2x, h2y, obs, dn, why);
   T ax, ay;
-  policy_action<T>(&P, A, ts->obs_dim, e, valid, A.step_count, e, obs, ax, ay);
+  policy_action<T>(&P, A, ts->obs_dim, e, valid, A.step_count, 0, e, obs, ax, ay);
   if (valid) {
     P.act[2 * e] = ax;
     P.act[2 * e + 1] = ay;

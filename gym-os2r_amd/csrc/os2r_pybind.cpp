@@ -41,6 +41,10 @@ PYBIND11_MODULE(_os2r_py, m) {
                                    addr done, addr term, addr why, addr act, addr eps, addr st) {
     return os2r_rollout_policy_noisy(H(h), n, P(w), flags, P(sigma), salt, P(ret), (int32_t*)P(len), P(obs), P(rew), (uint8_t*)P(done),
                                      P(term), (uint16_t*)P(why), P(act), P(eps), P(st)); }, nogil);
+  m.def("rollout_policy_scheduled", [](addr h, int n, addr w, int period, int first, int flags, addr sigma, uint32_t salt, addr ret,
+                                       addr len, addr obs, addr rew, addr done, addr term, addr why, addr act, addr eps, addr st) {
+    return os2r_rollout_policy_scheduled(H(h), n, P(w), period, first, flags, P(sigma), salt, P(ret), (int32_t*)P(len), P(obs), P(rew),
+                                         (uint8_t*)P(done), P(term), (uint16_t*)P(why), P(act), P(eps), P(st)); }, nogil);
   m.def("copy_envs", [](addr dst, addr src, addr index, int what, addr obs, addr st) {
     return os2r_copy_envs(H(dst), H(src), (const int32_t*)P(index), what, P(obs), P(st)); }, nogil);
   m.def("linearize", [](addr h, addr act, double eq, double ev, double ea, addr next, addr ja, addr jb, addr st) {

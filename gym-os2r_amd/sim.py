@@ -73,6 +73,12 @@ class _PybindLib:
                                            self._a(length), self._a(obs), self._a(rew), self._a(done), self._a(term),
                                            self._a(reason), self._a(act), self._a(eps), self._a(st))
 
+    def os2r_rollout_policy_scheduled(self, h, n, w, period, first, flags, sigma, salt, ret, length, obs, rew, done, term, reason, act,
+                                      eps, st):
+        return self.m.rollout_policy_scheduled(self._a(h), int(n), self._a(w), int(period), int(first), int(flags), self._a(sigma),
+                                               int(salt), self._a(ret), self._a(length), self._a(obs), self._a(rew), self._a(done),
+                                               self._a(term), self._a(reason), self._a(act), self._a(eps), self._a(st))
+
     def os2r_copy_envs(self, dst, src, index, what, obs, st):
         return self.m.copy_envs(self._a(dst), self._a(src), self._a(index), int(what), self._a(obs), self._a(st))
 
@@ -339,6 +345,66 @@ class HipSim:
         self._check(self._lib.os2r_rollout_policy(self._h, K, _ptr(w), flags, _ptr(ret), _ptr(length), _ptr(obs), _ptr(rew),
                                                   _ptr(done), _ptr(term), _ptr(why), self._stream()), "os2r_rollout_policy")
         return ret, length, ((obs, rew, done, term, why) if want_outputs else None)
+
+    def rollout_schedule(self, nsteps: int, weights, *, clock: str = "window", wrap: bool = False, first_slot: int = 0,
+                         tanh: bool = False, first_episode: bool = False, sigma=None, salt: int = 0, want_outputs: bool = False,
+                         want_terminal: bool = False, want_reasons: bool = False, want_actions: bool = False,
+                         want_noise: bool = False):
+        """`nsteps` env-steps with a time-scheduled linear policy in the loop (include/os2r.h: os2r_rollout_policy_scheduled; one
+        launch where os2r_rollout has a fused kernel): a table of T weight sets, each as rollout_policy takes one, of which every
+        environment evaluates the set of its slot in each env-step.
+        weights: [T, 2, D+1] shared by all environments or [N, T, 2, D+1] one table per environment.
+        clock: "window": t = first_slot + k in env-step k of the call; "episode": t = first_slot + the environment's elapsed
+        episode steps (episode_info()[0] at the top of the env-step; 0 right after a reset or an auto-reset).
+        The slot is min(t, T-1) -- the last set is held --, or t mod T with wrap.  On the window clock a window may be split:
+        K steps equal K1 steps followed by K - K1 steps with first_slot + K1, bit for bit.
+        sigma, salt, want_noise: the exploration noise of rollout_policy.  want_actions works with and without sigma:
+        rollout(K, actions) replays the window bit for bit.
+        -> (returns [N], lengths [N] int32, outputs | None, (actions [K, N, 2] | None, noise [K, N, 2] | None))."""
+        K = int(nsteps)
+        if K < 1:
+            raise ValueError("rollout_schedule: nsteps must be >= 1")
+        if clock not in ("window", "episode"):
+            raise ValueError(f"rollout_schedule: clock must be 'window' or 'episode', got {clock!r}")
+        if not 0 <= int(first_slot) < 2 ** 31:
+            raise ValueError("rollout_schedule: first_slot must be a non-negative 32-bit value")
+        if sigma is None and (want_noise or salt):
+            raise ValueError("rollout_schedule: want_noise and salt need sigma (sigma=0.0: the deterministic policy)")
+        if not 0 <= int(salt) < 2 ** 32:
+            raise ValueError("rollout_schedule: salt must be a 32-bit unsigned value")
+        sg, sg_flags = (None, 0) if sigma is None else self._sigma(sigma)
+        R = self.D + 1
+        if not isinstance(weights, torch.Tensor):
+            weights = torch.as_tensor(weights)
+        shape = tuple(weights.shape)
+        flags = ((abi.POLICY_TANH if tanh else 0) | (abi.POLICY_FIRST_EPISODE if first_episode else 0) |
+                 (abi.POLICY_CLOCK_EPISODE if clock == "episode" else 0) | (abi.POLICY_SCHEDULE_WRAP if wrap else 0))
+        if len(shape) == 3 and shape[0] >= 1 and shape[1:] == (2, R):
+            T, w = shape[0], weights
+        elif len(shape) == 4 and shape[0] == self.N and shape[1] >= 1 and shape[2:] == (2, R):
+            T, w = shape[1], weights.permute(1, 2, 3, 0)      # the kernel's layout: [T][2][D+1][N], env index fastest
+            flags |= abi.POLICY_PER_ENV
+        else:
+            raise ValueError(f"rollout_schedule: weights must be [T, 2, {R}] or [{self.N}, T, 2, {R}] with T >= 1, got {shape}")
+        if weights.dtype != self.dtype or weights.device != self.device:
+            raise ValueError(f"rollout_schedule: weights must be {self.dtype} on {self.device}, got {weights.dtype} on {weights.device}")
+        w = w.contiguous()
+        ret, length = self._new(self.N), self._new(self.N, dtype=torch.int32)
+        obs = rew = done = term = why = None
+        if want_outputs:
+            obs, rew = self._new(K, self.N, self.D), self._new(K, self.N)
+            done = self._new(K, self.N, dtype=torch.uint8)
+            term = self._new(K, self.N, self.D) if want_terminal else None
+            why = self._new(K, self.N, dtype=torch.int16) if want_reasons else None
+        act = self._new(K, self.N, 2) if want_actions else None
+        eps = self._new(K, self.N, 2) if want_noise else None
+        fn = getattr(self._lib, "os2r_rollout_policy_scheduled", None)
+        if fn is None:
+            raise Os2rError("this libos2r.so has no os2r_rollout_policy_scheduled")
+        self._check(fn(self._h, K, _ptr(w), T, int(first_slot), flags | sg_flags, _ptr(sg), int(salt), _ptr(ret), _ptr(length),
+                       _ptr(obs), _ptr(rew), _ptr(done), _ptr(term), _ptr(why), _ptr(act), _ptr(eps), self._stream()),
+                    "os2r_rollout_policy_scheduled")
+        return ret, length, ((obs, rew, done, term, why) if want_outputs else None), (act, eps)
 
     def reset(self, mask: Optional[torch.Tensor] = None):
         m = None if mask is None else self._in(mask, (self.N,), torch.uint8)

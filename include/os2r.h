@@ -41,8 +41,8 @@ extern "C" {
 
 #define OS2R_ABI_VERSION 6   /* os2r_create also takes configs stamped 5 (Os2rConfig did not change in 6) */
 #define OS2R_ABI_MINOR 1     /* entry points added within ABI 6 (os2r_abi_minor): 1: os2r_rollout_policy_noisy */
-/* os2r_copy_envs and, after it, os2r_linearize were added later without a new minor: a binding finds out whether they are
- * there by looking the symbol up */
+/* os2r_copy_envs and, after it, os2r_linearize and os2r_rollout_policy_scheduled were added later without a new minor: a binding
+ * finds out whether they are there by looking the symbol up */
 
 #define OS2R_MAX_DOF 5      /* yaw, pitch, boom_connector, hip, knee                       */
 #define OS2R_MAX_CAND 192   /* ground-contact candidate points of one model                */
@@ -303,6 +303,36 @@ OS2R_API int os2r_rollout_policy_noisy(Os2rSim* sim, int nsteps, const void* wei
                                        void* return_dev, int32_t* length_dev,
                                        void* obs_dev, void* reward_dev, uint8_t* done_dev, void* term_obs_dev,
                                        uint16_t* reason_dev, void* action_dev, void* noise_dev, void* stream);
+
+/* The same rollout with a time-scheduled linear policy (added within ABI 6 without a new minor: look the symbol up): the weights
+ * are a table of `period` sets, and in each env-step every environment evaluates the set of its slot.  For time-varying gains:
+ * TVLQR tracking of a recorded trajectory, the forward pass of iLQR, a periodic feed-forward-plus-feedback gait.
+ *   weights_dev  [period][2][D+1] shared by all environments, or [period][2][D+1][num_envs] (env index fastest) with
+ *                OS2R_POLICY_PER_ENV; row layout, evaluation order and squash of one set exactly as in os2r_rollout_policy
+ *   clock        in env-step k of the call (k = 0 .. nsteps-1) environment e takes t = first_slot + k, or, with
+ *                OS2R_POLICY_CLOCK_EPISODE, t = first_slot + steps[e]: the environment's elapsed episode steps as
+ *                os2r_get_episode_info would report them at the top of that env-step -- 0 in the first env-step after a reset or an
+ *                auto-reset (a negative count set through os2r_set_episode_info is taken as 0)
+ *   slot         s = min(t, period-1): the last set is held; or s = t mod period with OS2R_POLICY_SCHEDULE_WRAP
+ *                On the window clock one window of K env-steps equals two of K1 and K2 = K - K1 env-steps, the second with
+ *                first_slot + K1, bit for bit.
+ *   sigma_dev    nullable: NULL is the deterministic policy (salt must then be 0, noise_dev NULL); otherwise the noise is that of
+ *                os2r_rollout_policy_noisy, bit for bit: same stream, same counter, same flags (OS2R_POLICY_SIGMA_PER_ENV)
+ *   action_dev   [nsteps][num_envs][2] (nullable): the applied actions, with and without sigma: os2r_rollout on them replays the
+ *                window bit for bit
+ *   noise_dev    [nsteps][num_envs][2] (nullable; needs sigma_dev)
+ * Everything else -- returns, lengths, OS2R_POLICY_FIRST_EPISODE, the per-step outputs, step counter += nsteps, no violation
+ * counting, the handle's done-reason and done-mask buffers not written, one fused launch or the launch loop -- as
+ * os2r_rollout_policy.  period = 1 is os2r_rollout_policy (_noisy) itself.  Both of those refuse the two flag bits below.
+ * Errors: OS2R_ERR_INVALID for nsteps < 1, period < 1, first_slot < 0, a null weights_dev, an unknown flag bit, noise_dev without
+ * sigma_dev, a non-zero salt without sigma_dev (os2r_last_error says which).                                                    */
+#define OS2R_POLICY_CLOCK_EPISODE 16 /* slot from the environment's elapsed episode steps, not the window's step index */
+#define OS2R_POLICY_SCHEDULE_WRAP 32 /* slot = t mod period; else t is held at period-1 */
+OS2R_API int os2r_rollout_policy_scheduled(Os2rSim* sim, int nsteps, const void* weights_dev, int32_t period,
+                                           int32_t first_slot, int32_t flags, const void* sigma_dev, uint32_t salt,
+                                           void* return_dev, int32_t* length_dev,
+                                           void* obs_dev, void* reward_dev, uint8_t* done_dev, void* term_obs_dev,
+                                           uint16_t* reason_dev, void* action_dev, void* noise_dev, void* stream);
 
 /* Model-specialised kernels.  A robot that is not one of the four compiled-in reference variants
  * runs on generic kernels that read its constants through scalar loads (about half the speed).
