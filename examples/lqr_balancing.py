@@ -2,6 +2,7 @@
 """Discrete-time LQR about a held posture of Monopod-nonorm-balance-v1, from the simulator's own step Jacobians.
 
   python examples/lqr_balancing.py [--envs 1024] [--steps 500] [--settle 300] [--riccati-iters 500] [--eps 1e-4]
+                                   [--riccati {torch,device}]
 
   1. every environment runs a simple posture PD on hip and knee (the on-device linear policy of os2r_rollout_policy, written
      onto the raw observation slots) for --settle env-steps: the posture it holds is the linearisation point;
@@ -11,6 +12,8 @@
      environment;
   4. the gain goes back onto the observation slots as per-environment [2, D+1] weights, a = clip(a0 - K(x - x0)); state
      components the task does not observe (the boom's yaw, the pitch rate) drop out of the law;
+     with --riccati device, 3. and 4. are one os2r_lqr_gains launch (HipSim.lqr_gains: every iteration of every environment
+     and the weights); the torch recursion then runs only to print the largest difference between the two gains;
   5. from the same start, --steps env-steps run closed-loop on the device under the PD alone and under the LQR law.
 Nothing but the printed numbers leaves the device.  The script prints what happened; it claims no control quality: a
 quotient across a change of contact mode is a secant, the default eps is not tuned, and the truncated law is not the
@@ -63,6 +66,8 @@ def main():
     ap.add_argument("--kp", type=float, default=8.0)
     ap.add_argument("--kd", type=float, default=0.15)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--riccati", choices=("torch", "device"), default="torch",
+                    help="where the Riccati recursion runs: a torch loop, or one os2r_lqr_gains launch")
     args = ap.parse_args()
     N = args.envs
     env = g.make("Monopod-nonorm-balance-v1", num_envs=N, seed=args.seed)
@@ -90,8 +95,8 @@ def main():
     # 2. Jacobians about the held posture and the PD's action there
     obs_s = sim.copy_envs_from(sim, want_obs=True)
     a_s = (torch.einsum("njd,nd->nj", W_pd[:, :, :D], obs_s) + W_pd[:, :, D]).clamp(-1.0, 1.0)
-    _, _, A, B = sim.linearize(a_s, args.eps, want_next=False)
-    A, B = A.contiguous(), B.contiguous()
+    _, _, A_lin, B_lin = sim.linearize(a_s, args.eps, want_next=False)
+    A, B = A_lin.contiguous(), B_lin.contiguous()
     rho = torch.linalg.eigvals(A).abs().max(dim=1).values
     print(f"linearised {N} env-steps in one launch: spectral radius of A median {float(rho.median()):.4f} max {float(rho.max()):.4f}, "
           f"|B| max {float(B.abs().max()):.3e}", flush=True)
@@ -116,7 +121,19 @@ def main():
           flush=True)
 
     # 4. + 5. both laws from the same start, closed-loop on the device
-    W_lqr = weights_of_gain(K, a_s, obs_s, cols)
+    if args.riccati == "device":
+        # 3. + 4. again, in one launch: Q and R are host values there, the weights come back in the policy's layout
+        Kd, _, flags, Wd = sim.lqr_gains(A_lin, B_lin, torch.diag(qdiag).cpu(), 0.1 * torch.eye(2, dtype=torch.float64),
+                                         knots=1, sweeps=args.riccati_iters, actions=a_s, obs=obs_s, want_weights=True)
+        Kd, refused = Kd[0], flags[0] != 0
+        both = ok & ~refused
+        diff = float((Kd - K)[both].abs().max()) if bool(both.any()) else float("nan")
+        print(f"Riccati on the device: one launch of {args.riccati_iters} sweeps, {int(refused.sum())} of {N} environments refused in "
+              f"the last sweep; largest |K_device - K_torch| {diff:.3e} (|K_torch| max {float(K[both].abs().max()) if bool(both.any()) else 0.0:.3e})",
+              flush=True)
+        W_lqr = torch.where(refused[:, None, None], W_pd, Wd[:, 0]).contiguous()        # a refused problem falls back to the PD
+    else:
+        W_lqr = weights_of_gain(K, a_s, obs_s, cols)
     results = {}
     for name, W in (("PD only", W_pd), ("LQR", W_lqr)):
         sim.restore(start)

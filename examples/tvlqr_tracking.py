@@ -2,6 +2,7 @@
 """Time-varying LQR tracking of a recorded trajectory of Monopod-nonorm-balance-v1, gains from the simulator's own Jacobians.
 
   python examples/tvlqr_tracking.py [--envs 1024] [--steps 100] [--settle 300] [--pulse 0.4] [--perturb 0.02] [--eps 1e-4]
+                                    [--riccati {torch,device}]
 
   1. one environment runs the posture PD of lqr_balancing.py plus a hip-torque pulse for K = --steps env-steps: the nominal
      trajectory x_k, a_k (a_k the applied, clipped action);
@@ -12,6 +13,8 @@
      --envs copies of knot 0, each perturbed, track the nominal in ONE launch (HipSim.rollout_schedule, window clock) -- against
      the open-loop replay of the nominal actions from the same starts (HipSim.rollout);
   6. both deviations from the nominal observations are printed.
+With --riccati device, 4. and the table of 5. are one os2r_lqr_gains launch (HipSim.lqr_gains) on the linearize output as it
+is; the torch recursion then runs only to print the largest difference between the two sets of gains.
 Nothing but the printed numbers leaves the device.  The script prints what happened; it claims no control quality: a quotient
 across a change of contact mode is a secant, the default eps is not tuned, state components the task does not observe drop out
 of the law, and the actions saturate.
@@ -38,6 +41,8 @@ def main():
     ap.add_argument("--kp", type=float, default=8.0)
     ap.add_argument("--kd", type=float, default=0.15)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--riccati", choices=("torch", "device"), default="torch",
+                    help="where the Riccati recursion runs: a torch loop, or one os2r_lqr_gains launch")
     args = ap.parse_args()
     N, K = args.envs, args.steps
     # one task, three handles: the nominal (1 environment), the knots (K lanes), the trackers (N environments); no TimeLimit
@@ -79,8 +84,8 @@ def main():
 
     # 3. every knot's Jacobians in one launch
     obs_k = knots.copy_envs_from(knots, want_obs=True)                                # the observation at each knot
-    _, _, A, B = knots.linearize(a_nom, args.eps, want_next=False)
-    A, B = A.contiguous(), B.contiguous()
+    _, _, A_lin, B_lin = knots.linearize(a_nom, args.eps, want_next=False)
+    A, B = A_lin.contiguous(), B_lin.contiguous()
     print(f"linearised {K} knots in one launch: |A| max {float(A.abs().max()):.3e}, |B| max {float(B.abs().max()):.3e}", flush=True)
 
     # 4. backward Riccati recursion
@@ -102,7 +107,17 @@ def main():
     print(f"Riccati: {int(ok.sum())} of {K} gains finite, |K_k| max {float(gains.abs().max()):.3e}", flush=True)
 
     # 5. the table of weights (one set per knot: weights_of_gain takes the knots as its batch) and the two runs
-    table = weights_of_gain(gains, a_nom, obs_k, cols)                                # [K, 2, D+1]
+    if args.riccati == "device":
+        # 4. + 5. again, in one launch: K knots of one trajectory, the table in rollout_schedule's layout
+        Kd, _, flags, Wd = knots.lqr_gains(A_lin, B_lin, Q.cpu(), R.cpu(), knots=K, actions=a_nom, obs=obs_k, want_weights=True)
+        Kd, refused = Kd[:, 0], flags[:, 0] != 0
+        both = ok & ~refused
+        diff = float((Kd - gains)[both].abs().max()) if bool(both.any()) else float("nan")
+        print(f"Riccati on the device: one launch, {int(refused.sum())} of {K} knots refused; largest |K_device - K_torch| {diff:.3e}",
+              flush=True)
+        table = torch.where(refused[:, None, None], weights_of_gain(gains, a_nom, obs_k, cols), Wd[0]).contiguous()
+    else:
+        table = weights_of_gain(gains, a_nom, obs_k, cols)                            # [K, 2, D+1]
     trk.copy_envs_from(knots, 0)                                                      # every tracker starts as knot 0 ...
     q, qd = trk.get_state()
     gen = torch.Generator(device=dev).manual_seed(args.seed + 1)

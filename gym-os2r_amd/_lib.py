@@ -17,7 +17,7 @@ _lib = None
 
 # every symbol include/os2r.h declares
 SYMBOLS = ["os2r_abi_version", "os2r_abi_minor", "os2r_create", "os2r_destroy", "os2r_reset", "os2r_step",
-           "os2r_rollout", "os2r_rollout_policy", "os2r_rollout_policy_noisy", "os2r_rollout_policy_scheduled", "os2r_copy_envs", "os2r_linearize", "os2r_get_state", "os2r_set_state", "os2r_get_solver_state", "os2r_set_solver_state", "os2r_get_action_history", "os2r_set_action_history",
+           "os2r_rollout", "os2r_rollout_policy", "os2r_rollout_policy_noisy", "os2r_rollout_policy_scheduled", "os2r_copy_envs", "os2r_linearize", "os2r_lqr_gains", "os2r_get_state", "os2r_set_state", "os2r_get_solver_state", "os2r_set_solver_state", "os2r_get_action_history", "os2r_set_action_history",
            "os2r_set_params", "os2r_get_params", "os2r_get_episode_info", "os2r_set_episode_info", "os2r_get_action_violations",
            "os2r_get_step_count",
            "os2r_set_step_count", "os2r_bench_steps", "os2r_bench_steps_multi", "os2r_set_work_counters", "os2r_set_done_reasons", "os2r_set_done_mask", "os2r_get_violation_mirror", "os2r_model_is_compiled_in",
@@ -54,6 +54,8 @@ def load():
                                                   vp, vp, vp, vp, vp]
     lib.os2r_copy_envs.argtypes = [vp, vp, vp, C.c_int32, vp, vp]
     lib.os2r_linearize.argtypes = [vp, vp, C.POINTER(C.c_double), vp, vp, vp, vp]
+    lib.os2r_lqr_gains.argtypes = [vp, C.c_int32, C.c_int64, C.c_int32, vp, vp, C.POINTER(C.c_double), C.POINTER(C.c_double), vp, vp, vp, u8p,
+                                   vp, vp, vp, vp]
     lib.os2r_get_solver_state.argtypes = [vp, vp, vp, vp]
     lib.os2r_set_solver_state.argtypes = [vp, vp, vp, vp]
     lib.os2r_get_state.argtypes = [vp, vp, vp, vp]

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "os2r_kernels.hpp"
+#include "os2r_lqr.hpp"
 
 using namespace os2r;
 
@@ -567,6 +568,34 @@ int do_linearize(Os2rSim* s, const void* actions, const double* eps, void* next,
   return OS2R_OK;
 }
 
+// os2r_lqr_gains: one launch; the handle gives the dtype, nq and the observation layout and is not touched
+template <typename T>
+int do_lqr_gains(Os2rSim* s, int nknots, long long ntraj, int sweeps, const void* a, const void* b, const double* q, const double* r,
+                 const void* p_final, void* gain, void* p_out, uint8_t* flag, const void* actions, const void* obs, void* weights,
+                 hipStream_t st) {
+  LqrArgs<T> p;
+  std::memset(&p, 0, sizeof(p));
+  const int nq = s->nq, n = 2 * nq;
+  p.a = (const T*)a; p.b = (const T*)b; p.p_final = (const T*)p_final; p.p_out = (T*)p_out; p.gain = (T*)gain; p.flag = flag;
+  p.actions = (const T*)actions; p.obs = (const T*)obs; p.weights = (T*)weights;
+  p.M = ntraj; p.K = nknots; p.sweeps = sweeps; p.D = s->D;
+  const Os2rTaskSpec& t = s->cfg.task;
+  for (int d = 0; d < OS2R_MAX_OBS; ++d) {
+    p.slot_col[d] = -1;
+    if (d >= s->D) continue;
+    if (t.obs_kind[d] == OS2R_OBS_POS_RAW || t.obs_kind[d] == OS2R_OBS_POS_PERIODIC_RAW) p.slot_col[d] = t.obs_src[d];
+    if (t.obs_kind[d] == OS2R_OBS_VEL_RAW) p.slot_col[d] = nq + t.obs_src[d];
+  }
+  p.r00 = (T)r[0]; p.r01 = (T)r[1]; p.r11 = (T)r[3];
+  for (int i = 0; i < n * n; ++i) p.q[i] = (T)q[i];
+  if (launch_lqr_gains<T>(nq, p, st) != 0) {
+    s->err = "os2r_lqr_gains: no kernel for this chain length";
+    return OS2R_ERR_INVALID;
+  }
+  HIP_TRY(s, hipGetLastError());
+  return OS2R_OK;
+}
+
 void free_all(Os2rSim* s) {
   for (void* p : s->allocs) (void)hipFree(p);
   s->allocs.clear();
@@ -810,6 +839,38 @@ int os2r_linearize(Os2rSim* sim, const void* actions_dev, const double eps[3], v
   DeviceGuard guard(sim->cfg.device);
   return sim->cfg.dtype == OS2R_F64 ? do_linearize<double>(sim, actions_dev, eps, next_dev, a_dev, b_dev, (hipStream_t)stream)
                                     : do_linearize<float>(sim, actions_dev, eps, next_dev, a_dev, b_dev, (hipStream_t)stream);
+}
+
+int os2r_lqr_gains(Os2rSim* sim, int32_t nknots, int64_t ntraj, int32_t sweeps, const void* a_dev, const void* b_dev,
+                   const double* q_host, const double* r_host, const void* p_final_dev, void* gain_dev, void* p_out_dev,
+                   uint8_t* flag_dev, const void* actions_dev, const void* obs_dev, void* weights_dev, void* stream) {
+  if (!sim) { g_create_error = "os2r_lqr_gains: null handle"; return OS2R_ERR_INVALID; }
+  if (nknots < 1) { sim->err = "os2r_lqr_gains: nknots must be >= 1"; return OS2R_ERR_INVALID; }
+  if (ntraj < 1) { sim->err = "os2r_lqr_gains: ntraj must be >= 1"; return OS2R_ERR_INVALID; }
+  if (ntraj > (int64_t)kLqrEnvs * 0x7fffffffll) { sim->err = "os2r_lqr_gains: ntraj exceeds what one launch covers"; return OS2R_ERR_INVALID; }
+  if (sweeps < 1) { sim->err = "os2r_lqr_gains: sweeps must be >= 1"; return OS2R_ERR_INVALID; }
+  if (!a_dev) { sim->err = "os2r_lqr_gains: null a_dev"; return OS2R_ERR_INVALID; }
+  if (!b_dev) { sim->err = "os2r_lqr_gains: null b_dev"; return OS2R_ERR_INVALID; }
+  if (!q_host) { sim->err = "os2r_lqr_gains: null q_host"; return OS2R_ERR_INVALID; }
+  if (!r_host) { sim->err = "os2r_lqr_gains: null r_host"; return OS2R_ERR_INVALID; }
+  const int n = 2 * sim->nq;
+  // (bit patterns: the library is built without NaN semantics, see validate)
+  for (int i = 0; i < n * n; ++i)
+    if (!is_finite(&q_host[i])) { sim->err = "os2r_lqr_gains: Q must be finite"; return OS2R_ERR_INVALID; }
+  for (int i = 0; i < 4; ++i)
+    if (!is_finite(&r_host[i])) { sim->err = "os2r_lqr_gains: R must be finite"; return OS2R_ERR_INVALID; }
+  for (int i = 0; i < n; ++i)
+    for (int j = i + 1; j < n; ++j)
+      if (q_host[i * n + j] != q_host[j * n + i]) { sim->err = "os2r_lqr_gains: Q must be exactly symmetric"; return OS2R_ERR_INVALID; }
+  if (r_host[1] != r_host[2]) { sim->err = "os2r_lqr_gains: R must be exactly symmetric"; return OS2R_ERR_INVALID; }
+  if (!gain_dev && !p_out_dev && !weights_dev) { sim->err = "os2r_lqr_gains: all outputs are null (gain, p_out, weights)"; return OS2R_ERR_INVALID; }
+  if (weights_dev && (!actions_dev || !obs_dev)) { sim->err = "os2r_lqr_gains: weights need actions_dev and obs_dev"; return OS2R_ERR_INVALID; }
+  DeviceGuard guard(sim->cfg.device);
+  return sim->cfg.dtype == OS2R_F64
+             ? do_lqr_gains<double>(sim, nknots, ntraj, sweeps, a_dev, b_dev, q_host, r_host, p_final_dev, gain_dev, p_out_dev, flag_dev,
+                                    actions_dev, obs_dev, weights_dev, (hipStream_t)stream)
+             : do_lqr_gains<float>(sim, nknots, ntraj, sweeps, a_dev, b_dev, q_host, r_host, p_final_dev, gain_dev, p_out_dev, flag_dev,
+                                   actions_dev, obs_dev, weights_dev, (hipStream_t)stream);
 }
 
 int os2r_get_state(Os2rSim* sim, void* q_dev, void* qd_dev, void* stream) {

@@ -50,6 +50,10 @@ PYBIND11_MODULE(_os2r_py, m) {
   m.def("linearize", [](addr h, addr act, double eq, double ev, double ea, addr next, addr ja, addr jb, addr st) {
     const double eps[3] = {eq, ev, ea};
     return os2r_linearize(H(h), P(act), eps, P(next), P(ja), P(jb), P(st)); }, nogil);
+  m.def("lqr_gains", [](addr h, int nknots, long long ntraj, int sweeps, addr a, addr b, addr q, addr r, addr pf, addr gain, addr pout,
+                        addr flag, addr act, addr obs, addr w, addr st) {
+    return os2r_lqr_gains(H(h), nknots, ntraj, sweeps, P(a), P(b), (const double*)P(q), (const double*)P(r), P(pf), P(gain), P(pout),
+                          (uint8_t*)P(flag), P(act), P(obs), P(w), P(st)); }, nogil);
   m.def("get_solver_state", [](addr h, addr l, addr f, addr st) { return os2r_get_solver_state(H(h), P(l), (uint32_t*)P(f), P(st)); }, nogil);
   m.def("set_solver_state", [](addr h, addr l, addr f, addr st) { return os2r_set_solver_state(H(h), P(l), (const uint32_t*)P(f), P(st)); }, nogil);
   m.def("get_state", [](addr h, addr q, addr qd, addr st) { return os2r_get_state(H(h), P(q), P(qd), P(st)); }, nogil);

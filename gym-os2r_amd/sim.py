@@ -86,6 +86,11 @@ class _PybindLib:
         return self.m.linearize(self._a(h), self._a(act), float(eps[0]), float(eps[1]), float(eps[2]), self._a(nxt), self._a(ja),
                                 self._a(jb), self._a(st))
 
+    def os2r_lqr_gains(self, h, nknots, ntraj, sweeps, a, b, q, r, pf, gain, pout, flag, act, obs, w, st):
+        return self.m.lqr_gains(self._a(h), int(nknots), int(ntraj), int(sweeps), self._a(a), self._a(b), 0 if q is None else C.addressof(q), 0 if r is None else C.addressof(r),
+                                self._a(pf), self._a(gain), self._a(pout), self._a(flag), self._a(act), self._a(obs), self._a(w),
+                                self._a(st))
+
     def os2r_get_action_history(self, h, w, o, st):
         return self.m.get_action_history(self._a(h), int(w), self._a(o), self._a(st))
 
@@ -652,6 +657,123 @@ class HipSim:
         self.linearize_into(a, eps, nxt, ja, jb)
         return (nxt[:self.nq] if want_next else None, nxt[self.nq:] if want_next else None,
                 ja.permute(2, 0, 1) if want_A else None, jb.permute(2, 0, 1) if want_B else None)
+
+    # -- LQR gains --------------------------------------------------------------------------
+    def _lqr_cost(self, Q, R):
+        """Q [2nq, 2nq] and R [2, 2] of lqr_gains() -> two ctypes double arrays (row-major), checked: host values, finite and
+        exactly symmetric (include/os2r.h: os2r_lqr_gains)."""
+        n = 2 * self.nq
+        out = []
+        for name, m, k in (("Q", Q, n), ("R", R, 2)):
+            try:
+                if isinstance(m, torch.Tensor):
+                    t = m.detach().to("cpu", torch.float64)
+                else:                              # (through numpy: torch would make float32 of a list of Python floats)
+                    import numpy as np
+                    t = torch.from_numpy(np.array(m, dtype=np.float64))
+            except (TypeError, ValueError, RuntimeError):
+                raise ValueError(f"lqr_gains: {name} must be a [{k}, {k}] array of numbers, got {type(m)}") from None
+            if tuple(t.shape) != (k, k):
+                raise ValueError(f"lqr_gains: {name} must have shape ({k}, {k}), got {tuple(t.shape)}")
+            if not bool(torch.isfinite(t).all()):
+                raise ValueError(f"lqr_gains: {name} must be finite")
+            if not bool((t == t.T).all()):
+                raise ValueError(f"lqr_gains: {name} must be exactly symmetric")
+            out.append((C.c_double * (k * k))(*t.reshape(-1).tolist()))
+        return out
+
+    def lqr_gains_into(self, A, B, Q, R, *, knots: int = 1, sweeps: int = 1, P_final=None, gains_out=None, P_out=None, flags_out=None,
+                       actions=None, obs=None, weights_out=None):
+        """Allocation-free variant of lqr_gains() on tensors in the kernel's layout (include/os2r.h: os2r_lqr_gains), the
+        trajectory index fastest: with K = knots, L = K M and n = 2nq, A [n, n, L], B [n, 2, L], P_final [n, n, M] or None (Q),
+        gains_out [K, 2, n, M], P_out [n, n, M] (may be P_final), flags_out [K, M] uint8, weights_out [K, 2, D+1, M] with
+        actions [L, 2] and obs [L, D]; each output may be None, not all of gains_out, P_out and weights_out.  Shapes, dtypes,
+        device and contiguity are checked before the library is called (it takes addresses)."""
+        n = 2 * self.nq
+        K, sweeps = int(knots), int(sweeps)
+        if K < 1 or sweeps < 1:
+            raise ValueError(f"lqr_gains: knots and sweeps must be >= 1, got {K} and {sweeps}")
+        q, r = self._lqr_cost(Q, R)
+        if not isinstance(A, torch.Tensor) or A.dim() != 3:
+            raise ValueError(f"lqr_gains: A must be a tensor of shape ({n}, {n}, knots * M)")
+        L = int(A.shape[2])
+        if L < K or L % K:
+            raise ValueError(f"lqr_gains: the {L} lanes of A are no multiple of knots = {K}")
+        M = L // K
+        if gains_out is None and P_out is None and weights_out is None:
+            raise ValueError("lqr_gains: nothing asked for (gains, P and weights are all off)")
+        if weights_out is not None and (actions is None or obs is None):
+            raise ValueError("lqr_gains: weights need actions and obs (the point each knot was linearised about)")
+        self._out(A, (n, n, L), self.dtype, "lqr_gains: A")
+        self._out(B, (n, 2, L), self.dtype, "lqr_gains: B")
+        self._out(P_final, (n, n, M), self.dtype, "lqr_gains: P_final")
+        self._out(gains_out, (K, 2, n, M), self.dtype, "lqr_gains: gains_out")
+        self._out(P_out, (n, n, M), self.dtype, "lqr_gains: P_out")
+        self._out(flags_out, (K, M), torch.uint8, "lqr_gains: flags_out")
+        self._out(weights_out, (K, 2, self.D + 1, M), self.dtype, "lqr_gains: weights_out")
+        if weights_out is not None:
+            self._out(actions, (L, 2), self.dtype, "lqr_gains: actions")
+            self._out(obs, (L, self.D), self.dtype, "lqr_gains: obs")
+        else:
+            actions = obs = None
+        if B is None:
+            raise ValueError("lqr_gains: B is required")
+        fn = getattr(self._lib, "os2r_lqr_gains", None)
+        if fn is None:
+            raise Os2rError("this libos2r.so has no os2r_lqr_gains")
+        self._check(fn(self._h, K, M, sweeps, _ptr(A), _ptr(B), q, r, _ptr(P_final), _ptr(gains_out), _ptr(P_out), _ptr(flags_out),
+                       _ptr(actions), _ptr(obs), _ptr(weights_out), self._stream()), "os2r_lqr_gains")
+
+    def lqr_gains(self, A, B, Q, R, *, knots: int = 1, sweeps: int = 1, P_final=None, actions=None, obs=None, want_gains: bool = True,
+                  want_P: bool = False, want_flags: bool = True, want_weights: bool = False):
+        """The backward Riccati recursion of L = knots * M independent LQR problems in one launch (include/os2r.h:
+        os2r_lqr_gains; the arithmetic and its order are spelled out there).  A [L, 2nq, 2nq] and B [L, 2nq, 2] as linearize()
+        returns them -- permuted views of the kernel's layout are taken without a copy, anything else is copied once --, lane
+        k * M + m is knot k of trajectory m (a knot handle filled knot-major by copy_envs).  Q [2nq, 2nq] and R [2, 2]: host
+        values, finite, exactly symmetric.  P_final [M, 2nq, 2nq] or None (Q): the cost-to-go behind the last knot.  The knots
+        are passed `sweeps` times from the last to the first, P carried across: knots=1 with many sweeps is the stationary
+        iteration, several knots with several sweeps the periodic one of a wrapped schedule.
+        -> (gains [K, M, 2, 2nq], P [M, 2nq, 2nq], flags [K, M] uint8, weights [M, K, 2, D+1]), None where not wanted; all are
+        permuted views of the kernel's layouts.  flags is 1 where a knot's 2 x 2 system R + B'PB was refused (not positive
+        definite, or not finite): that knot's gain is 0.  weights (needs actions [L, 2] and obs [L, D], the point each knot was
+        linearised about) is the per-environment table rollout_schedule takes for a handle of M environments, holding
+        a = a0 - K_k (x - x_k) on the raw observation slots; rollout_schedule's .contiguous() on it is a no-op."""
+        n = 2 * self.nq
+        K = int(knots)
+        if K < 1 or int(sweeps) < 1:
+            raise ValueError(f"lqr_gains: knots and sweeps must be >= 1, got {K} and {int(sweeps)}")
+        if not (want_gains or want_P or want_weights):
+            raise ValueError("lqr_gains: nothing asked for (gains, P and weights are all off)")
+        if want_weights and (actions is None or obs is None):
+            raise ValueError("lqr_gains: weights need actions and obs (the point each knot was linearised about)")
+        self._lqr_cost(Q, R)
+        for name, t, w in (("A", A, n), ("B", B, 2)):
+            if not isinstance(t, torch.Tensor) or t.dim() != 3 or tuple(t.shape[1:]) != (n, w):
+                raise ValueError(f"lqr_gains: {name} must be a tensor of shape (knots * M, {n}, {w}), got "
+                                 f"{tuple(getattr(t, 'shape', ())) or type(t)}")
+            if t.dtype != self.dtype or t.device != self.device:
+                raise ValueError(f"lqr_gains: {name} must be {self.dtype} on {self.device}, got {t.dtype} on {t.device}")
+        L = int(A.shape[0])
+        if int(B.shape[0]) != L:
+            raise ValueError(f"lqr_gains: A has {L} lanes, B {int(B.shape[0])}")
+        if L < K or L % K:
+            raise ValueError(f"lqr_gains: the {L} lanes of A are no multiple of knots = {K}")
+        M = L // K
+        a, b = A.permute(1, 2, 0).contiguous(), B.permute(1, 2, 0).contiguous()     # no copy for what linearize() returned
+        pf = None
+        if P_final is not None:
+            pf = self._in(P_final, (M, n, n)).permute(1, 2, 0).contiguous()
+        act = ob = None
+        if want_weights:
+            act, ob = self._in(actions, (L, 2)), self._in(obs, (L, self.D))
+        gains = self._new(K, 2, n, M) if want_gains else None
+        pout = self._new(n, n, M) if want_P else None
+        flags = self._new(K, M, dtype=torch.uint8) if want_flags else None
+        wts = self._new(K, 2, self.D + 1, M) if want_weights else None
+        self.lqr_gains_into(a, b, Q, R, knots=K, sweeps=sweeps, P_final=pf, gains_out=gains, P_out=pout, flags_out=flags, actions=act,
+                            obs=ob, weights_out=wts)
+        return (gains.permute(0, 3, 1, 2) if want_gains else None, pout.permute(2, 0, 1) if want_P else None, flags,
+                wts.permute(3, 0, 1, 2) if want_weights else None)
 
     def action_violations_into(self, dst: torch.Tensor, clear: bool = True):
         """Copy the running count of out-of-range caller actions into ``dst`` (one int32/uint32 element,

@@ -41,8 +41,8 @@ extern "C" {
 
 #define OS2R_ABI_VERSION 6   /* os2r_create also takes configs stamped 5 (Os2rConfig did not change in 6) */
 #define OS2R_ABI_MINOR 1     /* entry points added within ABI 6 (os2r_abi_minor): 1: os2r_rollout_policy_noisy */
-/* os2r_copy_envs and, after it, os2r_linearize and os2r_rollout_policy_scheduled were added later without a new minor: a binding
- * finds out whether they are there by looking the symbol up */
+/* os2r_copy_envs and, after it, os2r_linearize, os2r_rollout_policy_scheduled and os2r_lqr_gains were added later without a new
+ * minor: a binding finds out whether they are there by looking the symbol up */
 
 #define OS2R_MAX_DOF 5      /* yaw, pitch, boom_connector, hip, knee                       */
 #define OS2R_MAX_CAND 192   /* ground-contact candidate points of one model                */
@@ -456,6 +456,51 @@ OS2R_API int os2r_copy_envs(Os2rSim* dst, Os2rSim* src, const int32_t* index_dev
  * that is not finite or not > 0, or eps[2] >= 1; os2r_last_error names the cause.                                          */
 OS2R_API int os2r_linearize(Os2rSim* sim, const void* actions_dev, const double eps[3], void* next_dev, void* a_dev, void* b_dev,
                             void* stream);
+
+/* Batched backward Riccati recursion (time-varying or stationary discrete LQR) in one launch: the gains K_k of
+ * a = a0 - K_k (x - x_k) for many independent trajectories, from Jacobians in os2r_linearize's layout, written in the layout
+ * os2r_rollout_policy_scheduled reads.  The handle supplies the dtype, nq (n = 2 nq), the device and the task's observation
+ * layout and is only read, as by os2r_linearize: no write to state, counters, mirror or a buffer of the handle's, no allocation,
+ * no host synchronisation, stream-ordered.  nknots * ntraj need not be the handle's num_envs.
+ * With K = nknots, M = ntraj, L = K M, lane of (knot k, trajectory m) = k M + m; every device array in the handle's dtype:
+ *   a_dev       [n][n][L], os2r_linearize's a_dev of a handle whose environments are ordered knot-major
+ *   b_dev       [n][2][L]
+ *   q_host      [n][n] row-major doubles, r_host [2][2]: host memory, read before the call returns, passed as kernel arguments;
+ *               finite and exactly symmetric; rounded once to the handle's dtype
+ *   p_final_dev nullable, [n][n][M]: the cost-to-go behind the last knot, upper triangle (i <= j) read; NULL: Q.  p_out_dev may
+ *               alias it
+ *   gain_dev    nullable, [K][2][n][M]: K_k
+ *   p_out_dev   nullable, [n][n][M]: P after the last processed knot, both triangles
+ *   flag_dev    nullable, [K][M] uint8: 1 where the knot's 2 x 2 system was refused (below), else 0; the last sweep's verdict
+ *   weights_dev nullable, [K][2][D+1][M]: the OS2R_POLICY_PER_ENV table of os2r_rollout_policy_scheduled with period = K; needs
+ *               actions_dev [L][2] (the array given to os2r_linearize; clamped to [-1, 1] as there) and obs_dev [L][D] (the
+ *               observation at each knot, as os2r_copy_envs returns it)
+ *   sweeps      >= 1: the knots are passed `sweeps` times, each from k = K-1 down to 0, P carried across (nknots = 1: the
+ *               stationary iteration; several knots: the periodic Riccati iteration of a wrapped schedule); gains, flags and
+ *               weights are those of the last pass
+ * At least one of gain_dev, p_out_dev, weights_dev is required.
+ * Arithmetic (part of the contract): the handle's dtype, every product rounded on its own (no fused multiply-add), every sum of
+ * products sum_l x_l y_l evaluated as ((x_0 y_0 + x_1 y_1) + x_2 y_2) + ... with l ascending.  Per knot, A = A_k, B = B_k, P the
+ * current symmetric cost-to-go:
+ *   1. PB[i][c] = sum_l P[i][l] B[l][c];  S00 = R00 + sum_l B[l][0] PB[l][0],  S01 = R01 + sum_l B[l][0] PB[l][1],
+ *      S11 = R11 + sum_l B[l][1] PB[l][1]
+ *   2. det = S00 S11 - S01 S01;  ok = S00 > 0 and det > 0 and det finite
+ *   3. PA[i][j] = sum_l P[i][l] A[l][j];  G[c][j] = sum_l B[l][c] PA[l][j]
+ *   4. K[0][j] = (S11 G[0][j] - S01 G[1][j]) / det,  K[1][j] = (S00 G[1][j] - S01 G[0][j]) / det, one IEEE division each (in
+ *      fp32 too); a knot that is not ok gets K = 0 and flag 1, and the recursion goes on with that K (P <- Q + A^T P A)
+ *   5. for i <= j: P'[i][j] = (Q[i][j] + sum_l A[l][i] PA[l][j]) - (G[0][i] K[0][j] + G[1][i] K[1][j]),  P'[j][i] = P'[i][j]
+ *   6. weights: slot d of kind OS2R_OBS_POS_RAW / OS2R_OBS_POS_PERIODIC_RAW shows state column obs_src[d], of kind
+ *      OS2R_OBS_VEL_RAW column nq + obs_src[d]: W[k][j][d] = -K[j][column]; every other slot gets 0;
+ *      W[k][j][D] = a0_j - sum_d W[k][j][d] o0_d, the sum over the raw slots in slot order
+ * The library does not judge Q >= 0 or the conditioning: flag_dev is the caller's tool.
+ * Errors: OS2R_ERR_INVALID for a null handle (os2r_last_error(NULL)); nknots, ntraj or sweeps < 1; null a_dev, b_dev, q_host
+ * or r_host; a Q or R that is not finite or not symmetric; all outputs null; weights_dev without actions_dev or obs_dev;
+ * os2r_last_error names the cause.                                                                                          */
+OS2R_API int os2r_lqr_gains(Os2rSim* sim, int32_t nknots, int64_t ntraj, int32_t sweeps,
+                            const void* a_dev, const void* b_dev,
+                            const double* q_host, const double* r_host,
+                            const void* p_final_dev, void* gain_dev, void* p_out_dev, uint8_t* flag_dev,
+                            const void* actions_dev, const void* obs_dev, void* weights_dev, void* stream);
 
 /* Global step counter that keys the on-device action RNG. */
 OS2R_API int os2r_get_step_count(Os2rSim* sim, uint64_t* out);

@@ -1,0 +1,224 @@
+"""os2r_lqr_gains (include/os2r.h): the host side -- declaration, export, bindings, the unchanged ABI numbers, the null-handle
+refusal through both bindings, the resources of the eight kernels in the built library, the argument checks of
+HipSim.lqr_gains that need no device, and the numpy restatement the GPU tests compare with against the textbook recursion.
+No GPU needed."""
+import ctypes
+import importlib
+import os
+import re
+import shutil
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from conftest import ROOT
+from gym_os2r_amd import abi
+
+
+def test_lqr_gains_is_declared_exported_and_bound():
+    from gym_os2r_amd import _lib
+    with open(os.path.join(ROOT, "include", "os2r.h")) as f:
+        header = f.read()
+    assert re.search(r"OS2R_API int os2r_lqr_gains\s*\(Os2rSim\* sim, int32_t nknots, int64_t ntraj, int32_t sweeps,\s*"
+                     r"const void\* a_dev, const void\* b_dev,\s*const double\* q_host, const double\* r_host,\s*"
+                     r"const void\* p_final_dev, void\* gain_dev, void\* p_out_dev, uint8_t\* flag_dev,\s*"
+                     r"const void\* actions_dev, const void\* obs_dev, void\* weights_dev, void\* stream\);", header)
+    assert "os2r_lqr_gains" in _lib.SYMBOLS
+    lib = _lib.load()
+    assert hasattr(ctypes.CDLL(_lib.LIB_PATH), "os2r_lqr_gains") and len(lib.os2r_lqr_gains.argtypes) == 16
+    assert hasattr(importlib.import_module("gym_os2r_amd._os2r_py"), "lqr_gains")
+    if shutil.which("nm"):
+        out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
+        assert "os2r_lqr_gains" in {ln.split()[-1] for ln in out.splitlines() if ln.strip()}
+    with open(os.path.join(ROOT, "gym-os2r_amd", "csrc", "libos2r.map")) as f:
+        assert "os2r_*" in f.read()                      # the version script exports the C-ABI by its prefix
+    from gym_os2r_amd.sim import HipSim, _PybindLib
+    assert callable(HipSim.lqr_gains) and callable(HipSim.lqr_gains_into) and callable(_PybindLib.os2r_lqr_gains)
+
+
+def test_abi_numbers_stay():
+    """The entry point came without a new ABI minor: a binding looks the symbol up."""
+    from gym_os2r_amd import _lib
+    lib = _lib.load()
+    assert hasattr(lib, "os2r_lqr_gains")
+    assert lib.os2r_abi_version() == 6 and lib.os2r_abi_minor() == 1
+    assert importlib.import_module("gym_os2r_amd._os2r_py").abi_minor() == 1
+    with open(os.path.join(ROOT, "include", "os2r.h")) as f:
+        header = f.read()
+    assert re.search(r"#define OS2R_ABI_MINOR 1\b", header) and re.search(r"os2r_lqr_gains were added later without a new\s+\*?\s*minor", header)
+
+
+def test_null_handle_is_rejected_without_a_device():
+    from gym_os2r_amd import _lib
+    lib = _lib.load()
+    buf = (ctypes.c_double * 128)()
+    q = (ctypes.c_double * 100)()
+    r = (ctypes.c_double * 4)()
+    p = ctypes.cast(buf, ctypes.c_void_p)
+    assert lib.os2r_lqr_gains(None, 1, 1, 1, p, p, q, r, None, p, None, None, None, None, None, None) == abi.ERR_INVALID
+    assert b"os2r_lqr_gains" in lib.os2r_last_error(None) and b"null handle" in lib.os2r_last_error(None)
+    m = importlib.import_module("gym_os2r_amd._os2r_py")
+    a = ctypes.addressof(buf)
+    assert m.lqr_gains(0, 1, 1, 1, a, a, ctypes.addressof(q), ctypes.addressof(r), 0, a, 0, 0, 0, 0, 0, 0) == abi.ERR_INVALID
+    assert "os2r_lqr_gains" in m.last_error(0) and "null handle" in m.last_error(0)
+    from gym_os2r_amd.sim import _PybindLib
+    assert _PybindLib().os2r_lqr_gains(None, 1, 1, 1, p, p, q, r, None, p, None, None, None, None, None, None) == abi.ERR_INVALID
+
+
+def test_refusals_come_before_the_device_is_touched():
+    """Every cause of include/os2r.h has its own message in the entry point; Q and R are tested on their bit pattern (the library
+    is built without NaN semantics) before they are compared."""
+    with open(os.path.join(ROOT, "gym-os2r_amd", "csrc", "os2r_capi.hip")) as f:
+        src = f.read()
+    body = re.search(r"int os2r_lqr_gains\(.*?\n}\n", src, re.S).group(0)
+    for msg in ("null handle", "nknots must be >= 1", "ntraj must be >= 1", "sweeps must be >= 1", "null a_dev", "null b_dev", "null q_host",
+                "null r_host", "Q must be finite", "R must be finite", "Q must be exactly symmetric", "R must be exactly symmetric",
+                "all outputs are null", "weights need actions_dev and obs_dev"):
+        assert msg in body, msg
+    assert body.index("is_finite(&q_host[i])") < body.index("q_host[i * n + j] != q_host[j * n + i]") < body.index("DeviceGuard")
+    assert body.index("is_finite(&r_host[i])") < body.index("r_host[1] != r_host[2]") < body.index("DeviceGuard")
+
+
+def test_lqr_kernel_resources():
+    """All eight kernels ({float, double} x nq 2..5) are in the built library, and none uses scratch: private_segment_fixed_size 0
+    and no VGPR spill in the code-object metadata.  Two workgroups of the widest one fit a CU's LDS."""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import kernel_meta
+    from gym_os2r_amd import _lib
+    assert os.path.exists(os.path.join(kernel_meta.LLVM, "llvm-readelf")) and os.path.exists(_lib.LIB_PATH)
+    meta = kernel_meta.kernel_meta(_lib.LIB_PATH)
+    lqr = {k: v for k, v in meta.items() if "lqr_gains_kernel<" in k}
+    assert len(lqr) == 8, sorted(lqr)
+    for real in ("float", "double"):
+        for nq in (2, 3, 4, 5):
+            (name,) = [k for k in lqr if f"lqr_gains_kernel<{real}, {nq}>" in k]
+            m = lqr[name]
+            assert m["private_segment_fixed_size"] == 0 and m["vgpr_spill_count"] == 0, (name, m)
+            assert m["agpr_count"] == 0 and m["vgpr_count"] <= 256, (name, m)
+            assert 2 * m["group_segment_fixed_size"] <= 160 * 1024, (name, m)
+
+
+def _bare(dtype, n=8, nq=3, D=4):
+    """A HipSim that never met a device: enough of it for the checks that run before the library is called."""
+    import torch
+    from gym_os2r_amd.sim import HipSim
+    s = HipSim.__new__(HipSim)
+    s.N, s.nq, s.D, s.dtype, s.device = n, nq, D, dtype, torch.device("cpu")
+    s._h = None
+    s._lib = None      # reaching the library would raise AttributeError (or Os2rError), not ValueError
+    return s
+
+
+def test_python_argument_errors_need_no_device():
+    import torch
+    s = _bare(torch.float64)
+    n, L, D = 6, 8, 4
+    A, B = torch.zeros(L, n, n, dtype=torch.float64), torch.zeros(L, n, 2, dtype=torch.float64)
+    Q, R = torch.eye(n, dtype=torch.float64), 0.1 * torch.eye(2, dtype=torch.float64)
+    q, r = s._lqr_cost(Q.numpy(), [[0.1, 0.02], [0.02, 0.2]])
+    assert list(q) == Q.reshape(-1).tolist() and list(r) == [0.1, 0.02, 0.02, 0.2]
+    nan, inf = float("nan"), float("inf")
+    bad_q = []
+    for i, j, v in ((0, 0, nan), (1, 2, inf), (2, 1, -inf), (1, 2, 0.5)):
+        m = Q.clone()
+        m[i, j] = v
+        bad_q.append(m)
+    for bq in bad_q + [torch.eye(5, dtype=torch.float64), torch.zeros(n), "x", None]:
+        with pytest.raises(ValueError, match="lqr_gains: Q"):
+            s.lqr_gains(A, B, bq, R)
+    for br in ([[0.1, nan], [nan, 0.1]], [[inf, 0.0], [0.0, 0.1]], [[0.1, 0.01], [0.02, 0.1]], torch.eye(3), 0.1, None):
+        with pytest.raises(ValueError, match="lqr_gains: R"):
+            s.lqr_gains(A, B, Q, br)
+        with pytest.raises(ValueError, match="lqr_gains: R"):
+            s.lqr_gains_into(A.permute(1, 2, 0).contiguous(), B.permute(1, 2, 0).contiguous(), Q, br, gains_out=torch.zeros(1, 2, n, L, dtype=torch.float64))
+    with pytest.raises(ValueError, match="nothing asked for"):
+        s.lqr_gains(A, B, Q, R, want_gains=False, want_flags=True)
+    with pytest.raises(ValueError, match="weights need actions and obs"):
+        s.lqr_gains(A, B, Q, R, want_weights=True)
+    with pytest.raises(ValueError, match="weights need actions and obs"):
+        s.lqr_gains(A, B, Q, R, want_weights=True, actions=torch.zeros(L, 2, dtype=torch.float64))
+    for kw in (dict(knots=0), dict(sweeps=0), dict(knots=-2)):
+        with pytest.raises(ValueError, match="must be >= 1"):
+            s.lqr_gains(A, B, Q, R, **kw)
+    with pytest.raises(ValueError, match="no multiple of knots"):
+        s.lqr_gains(A, B, Q, R, knots=3)
+    with pytest.raises(ValueError, match="no multiple of knots"):
+        s.lqr_gains(A, B, Q, R, knots=16)
+    for a, b in ((A.float(), B), (A, B.float()), (A[:, :5], B), (A, B[:, :, :1]), (A.permute(1, 2, 0), B), (A, B[:4]), (A.numpy(), B), (A, None)):
+        with pytest.raises(ValueError, match="lqr_gains"):
+            s.lqr_gains(a, b, Q, R)
+    with pytest.raises(ValueError, match="expected shape"):
+        s.lqr_gains(A, B, Q, R, knots=2, P_final=torch.zeros(L, n, n, dtype=torch.float64))          # M = 4 here
+    with pytest.raises(ValueError, match="expected shape"):
+        s.lqr_gains(A, B, Q, R, want_weights=True, actions=torch.zeros(L, 2, dtype=torch.float64), obs=torch.zeros(L, D + 1, dtype=torch.float64))
+    # the kernel-layout variant: every tensor is what the kernel assumes, or the call is refused before the library is reached
+    a, b = torch.zeros(n, n, L, dtype=torch.float64), torch.zeros(n, 2, L, dtype=torch.float64)
+    K, M = 2, 4
+    g = torch.zeros(K, 2, n, M, dtype=torch.float64)
+    with pytest.raises(ValueError, match="nothing asked for"):
+        s.lqr_gains_into(a, b, Q, R, knots=K, flags_out=torch.zeros(K, M, dtype=torch.uint8))
+    with pytest.raises(ValueError, match="weights need actions and obs"):
+        s.lqr_gains_into(a, b, Q, R, knots=K, weights_out=torch.zeros(K, 2, D + 1, M, dtype=torch.float64))
+    act, obs = torch.zeros(L, 2, dtype=torch.float64), torch.zeros(L, D, dtype=torch.float64)
+    for kw in (dict(A=A, gains_out=g),                                                    # the public layout is not the kernel's
+               dict(A=a.float(), gains_out=g), dict(B=b[:, :1], gains_out=g),
+               dict(A=torch.zeros(n, L, n, dtype=torch.float64).permute(0, 2, 1), gains_out=g),      # not contiguous
+               dict(gains_out=torch.zeros(K, M, 2, n, dtype=torch.float64)), dict(gains_out=g.float()),
+               dict(P_out=torch.zeros(M, n, n, dtype=torch.float64)), dict(gains_out=g, P_final=torch.zeros(n, n, L, dtype=torch.float64)),
+               dict(gains_out=g, flags_out=torch.zeros(K, M, dtype=torch.int32)), dict(gains_out=g, flags_out=torch.zeros(M, K, dtype=torch.uint8)),
+               dict(weights_out=torch.zeros(K, 2, D, M, dtype=torch.float64), actions=act, obs=obs),
+               dict(weights_out=torch.zeros(K, 2, D + 1, M, dtype=torch.float64), actions=act[:4], obs=obs),
+               dict(weights_out=torch.zeros(K, 2, D + 1, M, dtype=torch.float64), actions=act, obs=obs.float()),
+               dict(gains_out=[0.0] * 8)):
+        args = dict(dict(A=a, B=b), **kw)
+        with pytest.raises(ValueError, match="lqr_gains"):
+            s.lqr_gains_into(args.pop("A"), args.pop("B"), Q, R, knots=K, **args)
+    # what linearize() returns is taken without a copy; anything else is copied once into the kernel's layout
+    view = torch.zeros(n, n, L, dtype=torch.float64).permute(2, 0, 1)
+    assert view.permute(1, 2, 0).contiguous().data_ptr() == view.data_ptr()
+    assert A.permute(1, 2, 0).contiguous().data_ptr() != A.data_ptr()
+
+
+def test_the_restatement_agrees_with_the_textbook_recursion():
+    """The numpy restatement of tests/test_gpu_lqr_gains.py (the GPU tests' yardstick) against K = (R + B'PB)^-1 B'PA,
+    P <- Q + A'P(A - BK), P <- (P + P') / 2 with linalg.solve in fp64, on the synthetic inputs: the same sums in another order,
+    so the two differ by rounding only -- a knot forms each entry from about 2n products (n <= 10) and passes it through a 2 x 2
+    solve whose condition is below 100 here, and the recursion contracts: 1e3 eps relative to the largest entry bounds it with
+    room (measured: 2e-15 in fp64, 1.5e-6 in fp32).  Nothing is refused and everything is finite."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from test_gpu_lqr_gains import R_COST, restate, synthetic
+    # what is restated is the header's text: its steps are there, in the order the restatement follows
+    with open(os.path.join(ROOT, "include", "os2r.h")) as f:
+        header = " ".join(f.read().split())
+    steps = ["1. PB[i][c] = sum_l P[i][l] B[l][c]", "S01 = R01 + sum_l B[l][0] PB[l][1]", "2. det = S00 S11 - S01 S01",
+             "3. PA[i][j] = sum_l P[i][l] A[l][j]; G[c][j] = sum_l B[l][c] PA[l][j]", "4. K[0][j] = (S11 G[0][j] - S01 G[1][j]) / det",
+             "5. for i <= j: P'[i][j] = (Q[i][j] + sum_l A[l][i] PA[l][j]) - (G[0][i] K[0][j] + G[1][i] K[1][j])",
+             "W[k][j][D] = a0_j - sum_d W[k][j][d] o0_d"]
+    at = [header.replace(" * ", " ").find(t) for t in steps]
+    assert all(a >= 0 for a in at) and at == sorted(at), at
+    for n, K, M, sweeps in ((10, 4, 70, 1), (4, 1, 3, 50)):
+        A, B, Q = synthetic(n, K * M)
+        P = np.repeat(Q[None], M, 0)
+        G = np.zeros((K, 2, n, M))
+        for _ in range(sweeps):
+            for k in range(K - 1, -1, -1):
+                a, b = A[:, :, k * M:(k + 1) * M].transpose(2, 0, 1), B[:, :, k * M:(k + 1) * M].transpose(2, 0, 1)
+                bt = b.transpose(0, 2, 1)
+                Kk = np.linalg.solve(R_COST + bt @ P @ b, bt @ P @ a)
+                P = Q + a.transpose(0, 2, 1) @ P @ (a - b @ Kk)
+                P = 0.5 * (P + P.transpose(0, 2, 1))
+                G[k] = Kk.transpose(1, 2, 0)
+        for dtype in (np.float64, np.float32):
+            g, p, f, w = restate(A, B, Q, R_COST, K, sweeps, dtype, P_final=np.repeat(Q[:, :, None], M, 2))
+            assert g.dtype == dtype and p.dtype == dtype and w is None
+            assert not f.any() and np.isfinite(g).all() and np.isfinite(p).all()
+            assert np.array_equal(p, p.transpose(1, 0, 2))
+            tol = 1e3 * np.finfo(dtype).eps
+            assert np.abs(g - G).max() <= tol * np.abs(G).max(), (n, dtype, np.abs(g - G).max() / np.abs(G).max())
+            assert np.abs(p - P.transpose(1, 2, 0)).max() <= tol * np.abs(P).max(), (n, dtype)
+    # the header's degenerate knot: B = 0, R = 0, A = I / 2, Q = P = I: refused, K = 0, P' = 1.25 I
+    I = np.eye(6)
+    g, p, f, _ = restate(0.5 * I[:, :, None], np.zeros((6, 2, 1)), I, np.zeros((2, 2)), 1, 1, np.float64)
+    assert f[0, 0] == 1 and not g.any() and np.array_equal(p[:, :, 0], 1.25 * I)
