@@ -15,13 +15,50 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("OS2R_LIBRARY") or os.path.join(_HERE, "libos2r.so")   # OS2R_LIBRARY: A/B builds of the same ABI
 _lib = None
 
-# every symbol include/os2r.h declares
-SYMBOLS = ["os2r_abi_version", "os2r_abi_minor", "os2r_create", "os2r_destroy", "os2r_reset", "os2r_step",
-           "os2r_rollout", "os2r_rollout_policy", "os2r_rollout_policy_noisy", "os2r_rollout_policy_scheduled", "os2r_copy_envs", "os2r_linearize", "os2r_lqr_gains", "os2r_get_state", "os2r_set_state", "os2r_get_solver_state", "os2r_set_solver_state", "os2r_get_action_history", "os2r_set_action_history",
-           "os2r_set_params", "os2r_get_params", "os2r_get_episode_info", "os2r_set_episode_info", "os2r_get_action_violations",
-           "os2r_get_step_count",
-           "os2r_set_step_count", "os2r_bench_steps", "os2r_bench_steps_multi", "os2r_set_work_counters", "os2r_set_done_reasons", "os2r_set_done_mask", "os2r_get_violation_mirror", "os2r_model_is_compiled_in",
-           "os2r_register_model_kernels", "os2r_last_error"]
+_vp, _i32 = C.c_void_p, C.c_int32
+_cfg, _model, _f64p = C.POINTER(abi.Os2rConfig), C.POINTER(abi.Os2rModel), C.POINTER(C.c_double)
+
+# Every entry point include/os2r.h declares, in the header's order, with its ctypes argument types: the one declaration both
+# bindings are made from (load() below; _PybindLib; tests/test_bindings_host.py holds it against the header).  The result is
+# c_int, except for os2r_last_error (c_char_p).
+ENTRY_POINTS = {
+    "os2r_abi_version": (),
+    "os2r_abi_minor": (),
+    "os2r_create": (_cfg, C.POINTER(_vp)),
+    "os2r_destroy": (_vp,),
+    "os2r_reset": (_vp,) * 4,
+    "os2r_step": (_vp,) * 7,
+    "os2r_rollout": (_vp, C.c_int) + (_vp,) * 7,
+    "os2r_rollout_policy": (_vp, C.c_int, _vp, _i32) + (_vp,) * 8,
+    "os2r_rollout_policy_noisy": (_vp, C.c_int, _vp, _i32, _vp, C.c_uint32) + (_vp,) * 10,
+    "os2r_rollout_policy_scheduled": (_vp, C.c_int, _vp, _i32, _i32, _i32, _vp, C.c_uint32) + (_vp,) * 10,
+    "os2r_model_is_compiled_in": (_model,),
+    "os2r_register_model_kernels": (_model, _i32, _i32, C.c_char_p),
+    "os2r_get_action_violations": (_vp, _vp, _i32, _vp),
+    "os2r_get_violation_mirror": (_vp, C.POINTER(_vp)),
+    "os2r_get_state": (_vp,) * 4,
+    "os2r_set_state": (_vp,) * 4,
+    "os2r_get_solver_state": (_vp,) * 4,
+    "os2r_set_solver_state": (_vp,) * 4,
+    "os2r_get_action_history": (_vp, C.c_int, _vp, _vp),
+    "os2r_set_action_history": (_vp, C.c_int, _vp, _vp),
+    "os2r_set_params": (_vp, C.c_int, _vp, _vp),
+    "os2r_get_params": (_vp, C.c_int, _vp, _vp),
+    "os2r_get_episode_info": (_vp,) * 5,
+    "os2r_set_episode_info": (_vp,) * 5,
+    "os2r_copy_envs": (_vp, _vp, _vp, _i32, _vp, _vp),
+    "os2r_linearize": (_vp, _vp, _f64p, _vp, _vp, _vp, _vp),
+    "os2r_lqr_gains": (_vp, _i32, C.c_int64, _i32, _vp, _vp, _f64p, _f64p) + (_vp,) * 8,
+    "os2r_get_step_count": (_vp, C.POINTER(C.c_uint64)),
+    "os2r_set_step_count": (_vp, C.c_uint64),
+    "os2r_bench_steps": (_vp, C.c_int, _vp, C.POINTER(C.c_float)),
+    "os2r_bench_steps_multi": (C.POINTER(_vp), C.POINTER(_vp), C.c_int, C.c_int),
+    "os2r_set_work_counters": (_vp, _vp),
+    "os2r_set_done_reasons": (_vp, _vp),
+    "os2r_set_done_mask": (_vp, _vp),
+    "os2r_last_error": (_vp,),
+}
+SYMBOLS = list(ENTRY_POINTS)
 
 
 class Os2rLibraryMissing(ImportError):
@@ -41,49 +78,95 @@ def load():
     # its own, and os2r_create sees no device through the first ("no HIP device visible").
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
-    vp, u8p = C.c_void_p, C.c_void_p
-    lib.os2r_abi_version.restype = C.c_int
-    lib.os2r_create.argtypes = [C.POINTER(abi.Os2rConfig), C.POINTER(vp)]
-    lib.os2r_destroy.argtypes = [vp]
-    lib.os2r_reset.argtypes = [vp, u8p, vp, vp]
-    lib.os2r_step.argtypes = [vp, vp, vp, vp, u8p, vp, vp]
-    lib.os2r_rollout.argtypes = [vp, C.c_int, vp, vp, vp, u8p, vp, vp, vp]
-    lib.os2r_rollout_policy.argtypes = [vp, C.c_int, vp, C.c_int32, vp, vp, vp, vp, u8p, vp, vp, vp]
-    lib.os2r_rollout_policy_noisy.argtypes = [vp, C.c_int, vp, C.c_int32, vp, C.c_uint32, vp, vp, vp, vp, u8p, vp, vp, vp, vp, vp]
-    lib.os2r_rollout_policy_scheduled.argtypes = [vp, C.c_int, vp, C.c_int32, C.c_int32, C.c_int32, vp, C.c_uint32, vp, vp, vp, vp, u8p,
-                                                  vp, vp, vp, vp, vp]
-    lib.os2r_copy_envs.argtypes = [vp, vp, vp, C.c_int32, vp, vp]
-    lib.os2r_linearize.argtypes = [vp, vp, C.POINTER(C.c_double), vp, vp, vp, vp]
-    lib.os2r_lqr_gains.argtypes = [vp, C.c_int32, C.c_int64, C.c_int32, vp, vp, C.POINTER(C.c_double), C.POINTER(C.c_double), vp, vp, vp, u8p,
-                                   vp, vp, vp, vp]
-    lib.os2r_get_solver_state.argtypes = [vp, vp, vp, vp]
-    lib.os2r_set_solver_state.argtypes = [vp, vp, vp, vp]
-    lib.os2r_get_state.argtypes = [vp, vp, vp, vp]
-    lib.os2r_set_state.argtypes = [vp, vp, vp, vp]
-    lib.os2r_get_action_history.argtypes = [vp, C.c_int, vp, vp]
-    lib.os2r_set_action_history.argtypes = [vp, C.c_int, vp, vp]
-    lib.os2r_set_params.argtypes = [vp, C.c_int, vp, vp]
-    lib.os2r_get_params.argtypes = [vp, C.c_int, vp, vp]
-    lib.os2r_get_episode_info.argtypes = [vp, vp, vp, vp, vp]
-    lib.os2r_set_episode_info.argtypes = [vp, vp, vp, vp, vp]
-    lib.os2r_get_action_violations.argtypes = [vp, vp, C.c_int32, vp]
-    lib.os2r_get_step_count.argtypes = [vp, C.POINTER(C.c_uint64)]
-    lib.os2r_set_step_count.argtypes = [vp, C.c_uint64]
-    lib.os2r_bench_steps.argtypes = [vp, C.c_int, vp, C.POINTER(C.c_float)]
-    lib.os2r_bench_steps_multi.argtypes = [C.POINTER(vp), C.POINTER(vp), C.c_int, C.c_int]
-    lib.os2r_set_work_counters.argtypes = [vp, vp]
-    lib.os2r_set_done_reasons.argtypes = [vp, vp]
-    lib.os2r_set_done_mask.argtypes = [vp, u8p]
-    lib.os2r_get_violation_mirror.argtypes = [vp, C.POINTER(vp)]
-    lib.os2r_model_is_compiled_in.argtypes = [C.POINTER(abi.Os2rModel)]
-    lib.os2r_register_model_kernels.argtypes = [C.POINTER(abi.Os2rModel), C.c_int32, C.c_int32, C.c_char_p]
-    lib.os2r_last_error.argtypes = [vp]
-    lib.os2r_last_error.restype = C.c_char_p
-    for name in SYMBOLS:
-        getattr(lib, name)  # AttributeError here means header and library disagree
-        if name != "os2r_last_error":
-            getattr(lib, name).restype = C.c_int
+    for name, argtypes in ENTRY_POINTS.items():
+        fn = getattr(lib, name)  # AttributeError here means header and library disagree
+        fn.argtypes = list(argtypes)
+        fn.restype = C.c_char_p if name == "os2r_last_error" else C.c_int
     if lib.os2r_abi_version() != abi.ABI_VERSION:
         raise ImportError("libos2r.so ABI version does not match gym_os2r_amd.abi")
     _lib = lib
     return lib
+
+
+def _a(x):
+    """What a pointer parameter is given, as the address the pybind11 module takes: None, an int, a c_void_p, a byref(...),
+    a ctypes array or a ctypes scalar."""
+    if x is None:
+        return 0
+    if type(x) is C.c_void_p:
+        return x.value or 0
+    if isinstance(x, int):
+        return x
+    return C.addressof(getattr(x, "_obj", x))      # byref(v) keeps v as ._obj
+
+
+def _s(x):
+    return x.decode() if isinstance(x, bytes) else x
+
+
+def _converter(argtype):
+    if argtype is C.c_char_p:
+        return _s
+    return _a if issubclass(argtype, (C.c_void_p, C._Pointer)) else int
+
+
+def _forward(name, argtypes):
+    """`def os2r_x(self, a0, a1, ...): return self.m.x(_a(a0), int(a1), ...)`: the method of one entry point as it would be
+    written by hand, the converter of every argument fixed here.  (Made from source, not as a closure over a tuple of
+    converters: a loop over the arguments in every call cost a third more on os2r_step, and this one checks the arity.)"""
+    args = [f"a{i}" for i in range(len(argtypes))]
+    converted = ", ".join(f"{_converter(t).__name__}({a})" for t, a in zip(argtypes, args))
+    scope = {"_a": _a, "_s": _s, "__name__": __name__}
+    exec(f"def {name}(self, {', '.join(args)}): return self.m.{name[len('os2r_'):]}({converted})", scope)
+    scope[name].__qualname__ = f"_PybindLib.{name}"
+    return scope[name]
+
+
+class _PybindLib:
+    """Adapter giving the pybind11 module (`_os2r_py`) the call shapes of the ctypes library, so that gym_os2r_amd.sim is
+    binding-agnostic.  Selected with OS2R_BINDING=pybind11.  Every method is made from its row of ENTRY_POINTS (below the
+    class), with one converter per argument fixed there; written out are only the calls whose shape in the module differs
+    from the C one."""
+
+    def __init__(self):
+        import importlib
+        self.m = importlib.import_module("gym_os2r_amd._os2r_py")
+        if self.m.abi_version() != abi.ABI_VERSION:
+            raise ImportError("_os2r_py ABI version mismatch")
+
+    @staticmethod
+    def _result(out_ref, rc, value):
+        """The module returns (status, value) where the C call writes through a pointer."""
+        if out_ref is not None:
+            out_ref._obj.value = value
+        return rc
+
+    def os2r_create(self, cfg_ref, out_ref):
+        return self._result(out_ref, *self.m.create(_a(cfg_ref)))
+
+    def os2r_get_step_count(self, h, out_ref):
+        return self._result(out_ref, *self.m.get_step_count(_a(h)))
+
+    def os2r_get_violation_mirror(self, h, out_ref):
+        return self._result(out_ref, *self.m.get_violation_mirror(_a(h)))
+
+    def os2r_bench_steps(self, h, n, st, ms_ref):
+        if ms_ref is None:
+            return self.m.bench_enqueue(_a(h), int(n), _a(st))
+        return self._result(ms_ref, *self.m.bench_steps(_a(h), int(n), _a(st)))
+
+    def os2r_bench_steps_multi(self, sims, streams, count, nsteps):
+        n = range(int(count))                      # two arrays of c_void_p: an element reads as an int, or None for null
+        return self.m.bench_steps_multi([sims[i] or 0 for i in n], [streams[i] or 0 for i in n], int(nsteps))
+
+    def os2r_linearize(self, h, act, eps, nxt, ja, jb, st):
+        e = (0.0, 0.0, 0.0) if eps is None else eps      # the module takes three doubles: it has no null eps (0 is refused too)
+        return self.m.linearize(_a(h), _a(act), float(e[0]), float(e[1]), float(e[2]), _a(nxt), _a(ja), _a(jb), _a(st))
+
+    def os2r_last_error(self, h):
+        return self.m.last_error(_a(h)).encode()
+
+
+for _name, _argtypes in ENTRY_POINTS.items():
+    if _name not in vars(_PybindLib):
+        setattr(_PybindLib, _name, _forward(_name, _argtypes))

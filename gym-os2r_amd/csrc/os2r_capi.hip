@@ -135,6 +135,10 @@ namespace {
     }                                                                                          \
   } while (0)
 
+// The handle's arithmetic type, handed to `f` as a value of it: by_dtype(sim, [&](auto t) { return do_x<decltype(t)>(sim, ...); })
+template <typename F>
+int by_dtype(const Os2rSim* s, F&& f) { return s->cfg.dtype == OS2R_F64 ? f(double()) : f(float()); }
+
 template <typename T>
 void fill_model(const Os2rModel& m_in, bool contact, DevModel<T>& d) {
   Os2rModel m = m_in;
@@ -416,6 +420,19 @@ int dev_alloc(Os2rSim* s, void** p, size_t bytes) {
   return OS2R_OK;
 }
 
+// the robot and the task in the handle's dtype, as the kernels read them
+template <typename T>
+int upload_model(Os2rSim* s) {
+  DevModel<T> hm; DevTask<T> ht;
+  fill_model(s->cfg.model, s->cfg.contact != 0, hm); fill_task(s->cfg, ht);
+  int rc;
+  if ((rc = dev_alloc(s, &s->model_d, sizeof(hm)))) return rc;
+  if ((rc = dev_alloc(s, &s->task_d, sizeof(ht)))) return rc;
+  if (hipMemcpy(s->model_d, &hm, sizeof(hm), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(s->task_d, &ht, sizeof(ht), hipMemcpyHostToDevice) != hipSuccess) { s->err = "model upload failed"; return OS2R_ERR_HIP; }
+  return OS2R_OK;
+}
+
 // K env-steps with the linear policy in the loop: one launch of the fused kernel where os2r_rollout has a fused variant;
 // otherwise per env-step the policy kernel (state -> observation -> actions), the step launch with those actions and the
 // accumulation of the step's reward and done flag (same results)
@@ -596,6 +613,34 @@ int do_lqr_gains(Os2rSim* s, int nknots, long long ntraj, int sweeps, const void
   return OS2R_OK;
 }
 
+// What the three os2r_rollout_policy* entry points refuse before they touch the device, in one order.  An entry point fills in
+// its name, `unknown` (its flags without the bits it knows) and the rules that apply to it, each field by its name.
+struct PolicyCall {
+  const char* name; int nsteps; const void* weights; int unknown;
+  const char* missing = nullptr;   // an argument of the entry point's own that it requires and that is null: the refusal's text
+  bool scheduled = false;          // the scheduled entry point: the rules on the fields below; it is also the one of the three
+  int period = 1, first_slot = 0;  //   that names a null handle in os2r_last_error(NULL)
+  const void *sigma = nullptr, *noise = nullptr;
+  uint32_t salt = 0u;
+};
+
+int check_policy_call(Os2rSim* sim, const PolicyCall& c) {
+  auto refuse = [&](const char* why) {
+    (sim ? sim->err : g_create_error) = std::string(c.name) + ": " + why;
+    return (int)OS2R_ERR_INVALID;
+  };
+  if (!sim) return c.scheduled ? refuse("null handle") : (int)OS2R_ERR_INVALID;
+  if (c.nsteps < 1) return refuse("nsteps must be >= 1");
+  if (c.scheduled && c.period < 1) return refuse("period must be >= 1");
+  if (c.scheduled && c.first_slot < 0) return refuse("first_slot must be >= 0");
+  if (!c.weights) return refuse("null weights");
+  if (c.missing) return refuse(c.missing);
+  if (c.unknown) return refuse("unknown flag bits");
+  if (c.scheduled && !c.sigma && c.noise) return refuse("noise_dev needs sigma_dev");
+  if (c.scheduled && !c.sigma && c.salt != 0u) return refuse("a non-zero salt needs sigma_dev");
+  return OS2R_OK;
+}
+
 void free_all(Os2rSim* s) {
   for (void* p : s->allocs) (void)hipFree(p);
   s->allocs.clear();
@@ -677,21 +722,7 @@ int os2r_create(const Os2rConfig* cfg, Os2rSim** out) {
   if ((rc = dev_alloc(s, &s->b_rew, N * e))) return fail(rc);
   if ((rc = dev_alloc(s, &s->b_term, (size_t)s->D * N * e))) return fail(rc);
   if ((rc = dev_alloc(s, (void**)&s->b_done, N))) return fail(rc);
-  if (cfg->dtype == OS2R_F64) {
-    DevModel<double> hm; DevTask<double> ht;
-    fill_model(cfg->model, cfg->contact != 0, hm); fill_task(*cfg, ht);
-    if ((rc = dev_alloc(s, &s->model_d, sizeof(hm)))) return fail(rc);
-    if ((rc = dev_alloc(s, &s->task_d, sizeof(ht)))) return fail(rc);
-    if (hipMemcpy(s->model_d, &hm, sizeof(hm), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(s->task_d, &ht, sizeof(ht), hipMemcpyHostToDevice) != hipSuccess) { s->err = "model upload failed"; return fail(OS2R_ERR_HIP); }
-  } else {
-    DevModel<float> hm; DevTask<float> ht;
-    fill_model(cfg->model, cfg->contact != 0, hm); fill_task(*cfg, ht);
-    if ((rc = dev_alloc(s, &s->model_d, sizeof(hm)))) return fail(rc);
-    if ((rc = dev_alloc(s, &s->task_d, sizeof(ht)))) return fail(rc);
-    if (hipMemcpy(s->model_d, &hm, sizeof(hm), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(s->task_d, &ht, sizeof(ht), hipMemcpyHostToDevice) != hipSuccess) { s->err = "model upload failed"; return fail(OS2R_ERR_HIP); }
-  }
+  if ((rc = by_dtype(s, [&](auto t) { return upload_model<decltype(t)>(s); }))) return fail(rc);
   if (hipEventCreate(&s->ev0) != hipSuccess || hipEventCreate(&s->ev1) != hipSuccess) { s->err = "hipEventCreate failed"; return fail(OS2R_ERR_HIP); }
   // the violation mirror: pinned host memory that the device writes with plain system-scope stores (no atomics across PCIe)
   {
@@ -702,10 +733,8 @@ int os2r_create(const Os2rConfig* cfg, Os2rSim** out) {
     if (hipHostGetDevicePointer(&dp, hp, 0) != hipSuccess) { s->err = "hipHostGetDevicePointer (violation mirror) failed"; return fail(OS2R_ERR_HIP); }
     s->mirror_dev = (uint32_t*)dp;
   }
-  rc = cfg->dtype == OS2R_F64 ? init_params<double>(s, nullptr) : init_params<float>(s, nullptr);
-  if (rc) return fail(rc);
-  rc = cfg->dtype == OS2R_F64 ? do_reset<double>(s, nullptr, nullptr, nullptr) : do_reset<float>(s, nullptr, nullptr, nullptr);
-  if (rc) return fail(rc);
+  if ((rc = by_dtype(s, [&](auto t) { return init_params<decltype(t)>(s, nullptr); }))) return fail(rc);
+  if ((rc = by_dtype(s, [&](auto t) { return do_reset<decltype(t)>(s, nullptr, nullptr, nullptr); }))) return fail(rc);
   if (hipStreamSynchronize(nullptr) != hipSuccess) { s->err = "initial reset failed"; return fail(OS2R_ERR_HIP); }
   *out = s;
   return OS2R_OK;
@@ -723,87 +752,65 @@ int os2r_destroy(Os2rSim* sim) {
 int os2r_reset(Os2rSim* sim, const uint8_t* mask_dev, void* obs_dev, void* stream) {
   if (!sim) return OS2R_ERR_INVALID;
   DeviceGuard guard(sim->cfg.device);
-  return sim->cfg.dtype == OS2R_F64 ? do_reset<double>(sim, mask_dev, obs_dev, (hipStream_t)stream)
-                                    : do_reset<float>(sim, mask_dev, obs_dev, (hipStream_t)stream);
+  return by_dtype(sim, [&](auto t) { return do_reset<decltype(t)>(sim, mask_dev, obs_dev, (hipStream_t)stream); });
 }
 
 int os2r_step(Os2rSim* sim, const void* actions_dev, void* obs_dev, void* reward_dev, uint8_t* done_dev,
               void* term_obs_dev, void* stream) {
   if (!sim) return OS2R_ERR_INVALID;
   DeviceGuard guard(sim->cfg.device);
-  return sim->cfg.dtype == OS2R_F64
-             ? do_step<double>(sim, actions_dev, obs_dev, reward_dev, done_dev, term_obs_dev, (hipStream_t)stream)
-             : do_step<float>(sim, actions_dev, obs_dev, reward_dev, done_dev, term_obs_dev, (hipStream_t)stream);
+  return by_dtype(sim, [&](auto t) { return do_step<decltype(t)>(sim, actions_dev, obs_dev, reward_dev, done_dev, term_obs_dev, (hipStream_t)stream); });
 }
 
 int os2r_rollout(Os2rSim* sim, int nsteps, const void* actions_dev, void* obs_dev, void* reward_dev, uint8_t* done_dev,
                  void* term_obs_dev, uint16_t* reason_dev, void* stream) {
   if (!sim || nsteps < 1) return OS2R_ERR_INVALID;
   DeviceGuard guard(sim->cfg.device);
-  return sim->cfg.dtype == OS2R_F64
-             ? do_rollout<double>(sim, nsteps, actions_dev, obs_dev, reward_dev, done_dev, term_obs_dev, reason_dev, (hipStream_t)stream)
-             : do_rollout<float>(sim, nsteps, actions_dev, obs_dev, reward_dev, done_dev, term_obs_dev, reason_dev, (hipStream_t)stream);
+  return by_dtype(sim, [&](auto t) {
+    return do_rollout<decltype(t)>(sim, nsteps, actions_dev, obs_dev, reward_dev, done_dev, term_obs_dev, reason_dev, (hipStream_t)stream);
+  });
 }
 
 int os2r_rollout_policy(Os2rSim* sim, int nsteps, const void* weights_dev, int32_t flags, void* return_dev, int32_t* length_dev,
                         void* obs_dev, void* reward_dev, uint8_t* done_dev, void* term_obs_dev, uint16_t* reason_dev, void* stream) {
-  if (!sim) return OS2R_ERR_INVALID;
-  if (nsteps < 1) { sim->err = "os2r_rollout_policy: nsteps must be >= 1"; return OS2R_ERR_INVALID; }
-  if (!weights_dev) { sim->err = "os2r_rollout_policy: null weights"; return OS2R_ERR_INVALID; }
-  if (flags & ~(OS2R_POLICY_PER_ENV | OS2R_POLICY_TANH | OS2R_POLICY_FIRST_EPISODE)) {
-    sim->err = "os2r_rollout_policy: unknown flag bits";
-    return OS2R_ERR_INVALID;
-  }
+  const PolicyCall call{"os2r_rollout_policy", nsteps, weights_dev, flags & ~(OS2R_POLICY_PER_ENV | OS2R_POLICY_TANH | OS2R_POLICY_FIRST_EPISODE)};
+  if (int rc = check_policy_call(sim, call)) return rc;
   DeviceGuard guard(sim->cfg.device);
-  hipStream_t st = (hipStream_t)stream;
-  return sim->cfg.dtype == OS2R_F64
-             ? do_rollout_policy<double>(sim, nsteps, weights_dev, flags, return_dev, length_dev, obs_dev, reward_dev, done_dev, term_obs_dev, reason_dev, st)
-             : do_rollout_policy<float>(sim, nsteps, weights_dev, flags, return_dev, length_dev, obs_dev, reward_dev, done_dev, term_obs_dev, reason_dev, st);
+  return by_dtype(sim, [&](auto t) {
+    return do_rollout_policy<decltype(t)>(sim, nsteps, weights_dev, flags, return_dev, length_dev, obs_dev, reward_dev, done_dev, term_obs_dev,
+                                          reason_dev, (hipStream_t)stream);
+  });
 }
 
 int os2r_rollout_policy_noisy(Os2rSim* sim, int nsteps, const void* weights_dev, int32_t flags, const void* sigma_dev, uint32_t salt,
                               void* return_dev, int32_t* length_dev, void* obs_dev, void* reward_dev, uint8_t* done_dev,
                               void* term_obs_dev, uint16_t* reason_dev, void* action_dev, void* noise_dev, void* stream) {
-  if (!sim) return OS2R_ERR_INVALID;
-  if (nsteps < 1) { sim->err = "os2r_rollout_policy_noisy: nsteps must be >= 1"; return OS2R_ERR_INVALID; }
-  if (!weights_dev) { sim->err = "os2r_rollout_policy_noisy: null weights"; return OS2R_ERR_INVALID; }
-  if (!sigma_dev) { sim->err = "os2r_rollout_policy_noisy: null sigma"; return OS2R_ERR_INVALID; }
-  if (flags & ~(OS2R_POLICY_PER_ENV | OS2R_POLICY_TANH | OS2R_POLICY_FIRST_EPISODE | OS2R_POLICY_SIGMA_PER_ENV)) {
-    sim->err = "os2r_rollout_policy_noisy: unknown flag bits";
-    return OS2R_ERR_INVALID;
-  }
+  PolicyCall call{"os2r_rollout_policy_noisy", nsteps, weights_dev,
+                  flags & ~(OS2R_POLICY_PER_ENV | OS2R_POLICY_TANH | OS2R_POLICY_FIRST_EPISODE | OS2R_POLICY_SIGMA_PER_ENV)};
+  if (!sigma_dev) call.missing = "null sigma";
+  if (int rc = check_policy_call(sim, call)) return rc;
   DeviceGuard guard(sim->cfg.device);
-  hipStream_t st = (hipStream_t)stream;
-  return sim->cfg.dtype == OS2R_F64
-             ? do_rollout_policy<double>(sim, nsteps, weights_dev, flags, return_dev, length_dev, obs_dev, reward_dev, done_dev, term_obs_dev,
-                                         reason_dev, st, sigma_dev, salt, action_dev, noise_dev)
-             : do_rollout_policy<float>(sim, nsteps, weights_dev, flags, return_dev, length_dev, obs_dev, reward_dev, done_dev, term_obs_dev,
-                                        reason_dev, st, sigma_dev, salt, action_dev, noise_dev);
+  return by_dtype(sim, [&](auto t) {
+    return do_rollout_policy<decltype(t)>(sim, nsteps, weights_dev, flags, return_dev, length_dev, obs_dev, reward_dev, done_dev, term_obs_dev,
+                                          reason_dev, (hipStream_t)stream, sigma_dev, salt, action_dev, noise_dev);
+  });
 }
 
 int os2r_rollout_policy_scheduled(Os2rSim* sim, int nsteps, const void* weights_dev, int32_t period, int32_t first_slot, int32_t flags,
                                   const void* sigma_dev, uint32_t salt, void* return_dev, int32_t* length_dev, void* obs_dev,
                                   void* reward_dev, uint8_t* done_dev, void* term_obs_dev, uint16_t* reason_dev, void* action_dev,
                                   void* noise_dev, void* stream) {
-  if (!sim) { g_create_error = "os2r_rollout_policy_scheduled: null handle"; return OS2R_ERR_INVALID; }
-  if (nsteps < 1) { sim->err = "os2r_rollout_policy_scheduled: nsteps must be >= 1"; return OS2R_ERR_INVALID; }
-  if (period < 1) { sim->err = "os2r_rollout_policy_scheduled: period must be >= 1"; return OS2R_ERR_INVALID; }
-  if (first_slot < 0) { sim->err = "os2r_rollout_policy_scheduled: first_slot must be >= 0"; return OS2R_ERR_INVALID; }
-  if (!weights_dev) { sim->err = "os2r_rollout_policy_scheduled: null weights"; return OS2R_ERR_INVALID; }
-  if (flags & ~(OS2R_POLICY_PER_ENV | OS2R_POLICY_TANH | OS2R_POLICY_FIRST_EPISODE | OS2R_POLICY_SIGMA_PER_ENV |
-                OS2R_POLICY_CLOCK_EPISODE | OS2R_POLICY_SCHEDULE_WRAP)) {
-    sim->err = "os2r_rollout_policy_scheduled: unknown flag bits";
-    return OS2R_ERR_INVALID;
-  }
-  if (!sigma_dev && noise_dev) { sim->err = "os2r_rollout_policy_scheduled: noise_dev needs sigma_dev"; return OS2R_ERR_INVALID; }
-  if (!sigma_dev && salt != 0u) { sim->err = "os2r_rollout_policy_scheduled: a non-zero salt needs sigma_dev"; return OS2R_ERR_INVALID; }
+  PolicyCall call{"os2r_rollout_policy_scheduled", nsteps, weights_dev,
+                  flags & ~(OS2R_POLICY_PER_ENV | OS2R_POLICY_TANH | OS2R_POLICY_FIRST_EPISODE | OS2R_POLICY_SIGMA_PER_ENV |
+                            OS2R_POLICY_CLOCK_EPISODE | OS2R_POLICY_SCHEDULE_WRAP)};
+  call.scheduled = true; call.period = period; call.first_slot = first_slot;
+  call.sigma = sigma_dev; call.salt = salt; call.noise = noise_dev;
+  if (int rc = check_policy_call(sim, call)) return rc;
   DeviceGuard guard(sim->cfg.device);
-  hipStream_t st = (hipStream_t)stream;
-  return sim->cfg.dtype == OS2R_F64
-             ? do_rollout_policy<double>(sim, nsteps, weights_dev, flags, return_dev, length_dev, obs_dev, reward_dev, done_dev, term_obs_dev,
-                                         reason_dev, st, sigma_dev, salt, action_dev, noise_dev, period, first_slot)
-             : do_rollout_policy<float>(sim, nsteps, weights_dev, flags, return_dev, length_dev, obs_dev, reward_dev, done_dev, term_obs_dev,
-                                        reason_dev, st, sigma_dev, salt, action_dev, noise_dev, period, first_slot);
+  return by_dtype(sim, [&](auto t) {
+    return do_rollout_policy<decltype(t)>(sim, nsteps, weights_dev, flags, return_dev, length_dev, obs_dev, reward_dev, done_dev, term_obs_dev,
+                                          reason_dev, (hipStream_t)stream, sigma_dev, salt, action_dev, noise_dev, period, first_slot);
+  });
 }
 
 int os2r_copy_envs(Os2rSim* dst, Os2rSim* src, const int32_t* index_dev, int32_t what, void* obs_dev, void* stream) {
@@ -821,8 +828,7 @@ int os2r_copy_envs(Os2rSim* dst, Os2rSim* src, const int32_t* index_dev, int32_t
     return OS2R_ERR_INVALID;
   }
   DeviceGuard guard(dst->cfg.device);
-  return dst->cfg.dtype == OS2R_F64 ? do_copy<double>(dst, src, index_dev, what, obs_dev, (hipStream_t)stream)
-                                    : do_copy<float>(dst, src, index_dev, what, obs_dev, (hipStream_t)stream);
+  return by_dtype(dst, [&](auto t) { return do_copy<decltype(t)>(dst, src, index_dev, what, obs_dev, (hipStream_t)stream); });
 }
 
 int os2r_linearize(Os2rSim* sim, const void* actions_dev, const double eps[3], void* next_dev, void* a_dev, void* b_dev, void* stream) {
@@ -837,8 +843,7 @@ int os2r_linearize(Os2rSim* sim, const void* actions_dev, const double eps[3], v
   }
   if (eps[2] >= 1.0) { sim->err = "os2r_linearize: eps[2] (action step) must be < 1"; return OS2R_ERR_INVALID; }
   DeviceGuard guard(sim->cfg.device);
-  return sim->cfg.dtype == OS2R_F64 ? do_linearize<double>(sim, actions_dev, eps, next_dev, a_dev, b_dev, (hipStream_t)stream)
-                                    : do_linearize<float>(sim, actions_dev, eps, next_dev, a_dev, b_dev, (hipStream_t)stream);
+  return by_dtype(sim, [&](auto t) { return do_linearize<decltype(t)>(sim, actions_dev, eps, next_dev, a_dev, b_dev, (hipStream_t)stream); });
 }
 
 int os2r_lqr_gains(Os2rSim* sim, int32_t nknots, int64_t ntraj, int32_t sweeps, const void* a_dev, const void* b_dev,
@@ -866,11 +871,10 @@ int os2r_lqr_gains(Os2rSim* sim, int32_t nknots, int64_t ntraj, int32_t sweeps, 
   if (!gain_dev && !p_out_dev && !weights_dev) { sim->err = "os2r_lqr_gains: all outputs are null (gain, p_out, weights)"; return OS2R_ERR_INVALID; }
   if (weights_dev && (!actions_dev || !obs_dev)) { sim->err = "os2r_lqr_gains: weights need actions_dev and obs_dev"; return OS2R_ERR_INVALID; }
   DeviceGuard guard(sim->cfg.device);
-  return sim->cfg.dtype == OS2R_F64
-             ? do_lqr_gains<double>(sim, nknots, ntraj, sweeps, a_dev, b_dev, q_host, r_host, p_final_dev, gain_dev, p_out_dev, flag_dev,
-                                    actions_dev, obs_dev, weights_dev, (hipStream_t)stream)
-             : do_lqr_gains<float>(sim, nknots, ntraj, sweeps, a_dev, b_dev, q_host, r_host, p_final_dev, gain_dev, p_out_dev, flag_dev,
-                                   actions_dev, obs_dev, weights_dev, (hipStream_t)stream);
+  return by_dtype(sim, [&](auto t) {
+    return do_lqr_gains<decltype(t)>(sim, nknots, ntraj, sweeps, a_dev, b_dev, q_host, r_host, p_final_dev, gain_dev, p_out_dev, flag_dev,
+                                     actions_dev, obs_dev, weights_dev, (hipStream_t)stream);
+  });
 }
 
 int os2r_get_state(Os2rSim* sim, void* q_dev, void* qd_dev, void* stream) {

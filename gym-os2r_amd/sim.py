@@ -11,138 +11,11 @@ from typing import Optional
 import torch
 
 from . import _lib, abi
+from ._lib import _PybindLib
 
 
 class Os2rError(RuntimeError):
     pass
-
-
-class _PybindLib:
-    """Adapter giving the pybind11 module (`_os2r_py`) the call shapes of the ctypes library, so the
-    rest of this file is binding-agnostic.  Selected with OS2R_BINDING=pybind11."""
-
-    def __init__(self):
-        import importlib
-        self.m = importlib.import_module("gym_os2r_amd._os2r_py")
-        if self.m.abi_version() != abi.ABI_VERSION:
-            raise ImportError("_os2r_py ABI version mismatch")
-
-    @staticmethod
-    def _a(x):
-        if x is None:
-            return 0
-        v = getattr(x, "value", x)
-        return 0 if v is None else int(v)
-
-    def os2r_create(self, cfg_ref, out_ref):
-        rc, h = self.m.create(C.addressof(cfg_ref._obj))
-        out_ref._obj.value = h
-        return rc
-
-    def os2r_destroy(self, h):
-        return self.m.destroy(self._a(h))
-
-    def os2r_reset(self, h, mask, obs, st):
-        return self.m.reset(self._a(h), self._a(mask), self._a(obs), self._a(st))
-
-    def os2r_step(self, h, act, obs, rew, done, term, st):
-        return self.m.step(self._a(h), self._a(act), self._a(obs), self._a(rew), self._a(done), self._a(term), self._a(st))
-
-    def os2r_get_state(self, h, q, qd, st):
-        return self.m.get_state(self._a(h), self._a(q), self._a(qd), self._a(st))
-
-    def os2r_set_state(self, h, q, qd, st):
-        return self.m.set_state(self._a(h), self._a(q), self._a(qd), self._a(st))
-
-    def os2r_get_solver_state(self, h, lam, flags, st):
-        return self.m.get_solver_state(self._a(h), self._a(lam), self._a(flags), self._a(st))
-
-    def os2r_set_solver_state(self, h, lam, flags, st):
-        return self.m.set_solver_state(self._a(h), self._a(lam), self._a(flags), self._a(st))
-
-    def os2r_rollout(self, h, n, act, obs, rew, done, term, reason, st):
-        return self.m.rollout(self._a(h), int(n), self._a(act), self._a(obs), self._a(rew), self._a(done), self._a(term),
-                              self._a(reason), self._a(st))
-
-    def os2r_rollout_policy(self, h, n, w, flags, ret, length, obs, rew, done, term, reason, st):
-        return self.m.rollout_policy(self._a(h), int(n), self._a(w), int(flags), self._a(ret), self._a(length), self._a(obs),
-                                     self._a(rew), self._a(done), self._a(term), self._a(reason), self._a(st))
-
-    def os2r_rollout_policy_noisy(self, h, n, w, flags, sigma, salt, ret, length, obs, rew, done, term, reason, act, eps, st):
-        return self.m.rollout_policy_noisy(self._a(h), int(n), self._a(w), int(flags), self._a(sigma), int(salt), self._a(ret),
-                                           self._a(length), self._a(obs), self._a(rew), self._a(done), self._a(term),
-                                           self._a(reason), self._a(act), self._a(eps), self._a(st))
-
-    def os2r_rollout_policy_scheduled(self, h, n, w, period, first, flags, sigma, salt, ret, length, obs, rew, done, term, reason, act,
-                                      eps, st):
-        return self.m.rollout_policy_scheduled(self._a(h), int(n), self._a(w), int(period), int(first), int(flags), self._a(sigma),
-                                               int(salt), self._a(ret), self._a(length), self._a(obs), self._a(rew), self._a(done),
-                                               self._a(term), self._a(reason), self._a(act), self._a(eps), self._a(st))
-
-    def os2r_copy_envs(self, dst, src, index, what, obs, st):
-        return self.m.copy_envs(self._a(dst), self._a(src), self._a(index), int(what), self._a(obs), self._a(st))
-
-    def os2r_linearize(self, h, act, eps, nxt, ja, jb, st):
-        return self.m.linearize(self._a(h), self._a(act), float(eps[0]), float(eps[1]), float(eps[2]), self._a(nxt), self._a(ja),
-                                self._a(jb), self._a(st))
-
-    def os2r_lqr_gains(self, h, nknots, ntraj, sweeps, a, b, q, r, pf, gain, pout, flag, act, obs, w, st):
-        return self.m.lqr_gains(self._a(h), int(nknots), int(ntraj), int(sweeps), self._a(a), self._a(b), 0 if q is None else C.addressof(q), 0 if r is None else C.addressof(r),
-                                self._a(pf), self._a(gain), self._a(pout), self._a(flag), self._a(act), self._a(obs), self._a(w),
-                                self._a(st))
-
-    def os2r_get_action_history(self, h, w, o, st):
-        return self.m.get_action_history(self._a(h), int(w), self._a(o), self._a(st))
-
-    def os2r_set_action_history(self, h, w, i, st):
-        return self.m.set_action_history(self._a(h), int(w), self._a(i), self._a(st))
-
-    def os2r_set_params(self, h, f, s, st):
-        return self.m.set_params(self._a(h), int(f), self._a(s), self._a(st))
-
-    def os2r_get_params(self, h, f, d, st):
-        return self.m.get_params(self._a(h), int(f), self._a(d), self._a(st))
-
-    def os2r_get_episode_info(self, h, s, e, p, st):
-        return self.m.get_episode_info(self._a(h), self._a(s), self._a(e), self._a(p), self._a(st))
-
-    def os2r_set_episode_info(self, h, s, e, p, st):
-        return self.m.set_episode_info(self._a(h), self._a(s), self._a(e), self._a(p), self._a(st))
-
-    def os2r_get_action_violations(self, h, d, clear, st):
-        return self.m.get_action_violations(self._a(h), self._a(d), int(clear), self._a(st))
-
-    def os2r_get_step_count(self, h, out_ref):
-        rc, v = self.m.get_step_count(self._a(h))
-        out_ref._obj.value = v
-        return rc
-
-    def os2r_set_step_count(self, h, v):
-        return self.m.set_step_count(self._a(h), int(getattr(v, "value", v)))
-
-    def os2r_bench_steps(self, h, n, st, ms_ref):
-        if ms_ref is None:
-            return self.m.bench_enqueue(self._a(h), int(n), self._a(st))
-        rc, ms = self.m.bench_steps(self._a(h), int(n), self._a(st))
-        ms_ref._obj.value = ms
-        return rc
-
-    def os2r_set_work_counters(self, h, buf):
-        return self.m.set_work_counters(self._a(h), self._a(buf))
-
-    def os2r_set_done_reasons(self, h, buf):
-        return self.m.set_done_reasons(self._a(h), self._a(buf))
-
-    def os2r_set_done_mask(self, h, buf):
-        return self.m.set_done_mask(self._a(h), self._a(buf))
-
-    def os2r_get_violation_mirror(self, h, out_ref):
-        rc, v = self.m.get_violation_mirror(self._a(h))
-        out_ref._obj.value = v
-        return rc
-
-    def os2r_last_error(self, h):
-        return self.m.last_error(self._a(h)).encode()
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -249,10 +122,7 @@ class HipSim:
         terminal_obs [K,N,D] or None, reasons [K,N] int16 or None -- what K calls of step() return, bit for bit."""
         K = int(nsteps)
         a = None if actions is None else self._in(actions, (K, self.N, 2))
-        obs, rew = self._new(K, self.N, self.D), self._new(K, self.N)
-        done = self._new(K, self.N, dtype=torch.uint8)
-        term = self._new(K, self.N, self.D) if want_terminal else None
-        why = self._new(K, self.N, dtype=torch.int16) if want_reasons else None
+        obs, rew, done, term, why = self._steps_out(K, want_terminal, want_reasons)
         self._check(self._lib.os2r_rollout(self._h, K, _ptr(a), _ptr(obs), _ptr(rew), _ptr(done), _ptr(term), _ptr(why),
                                            self._stream()), "os2r_rollout")
         return obs, rew, done, term, why
@@ -265,6 +135,18 @@ class HipSim:
             raise ValueError(f"{what}: expected a contiguous {dtype} tensor of shape {tuple(shape)} on {self.device}, got "
                              f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))} on {getattr(t, 'device', None)}")
 
+    def _steps_out(self, K, want_terminal=False, want_reasons=False, given=None):
+        """The per-step outputs of a K-step rollout, (obs [K,N,D], rew [K,N], done [K,N] uint8, term [K,N,D], reasons [K,N] int16):
+        new tensors, term and reasons only where wanted; or the caller's own (`given`), checked."""
+        specs = (("obs", (K, self.N, self.D), self.dtype), ("rew", (K, self.N), self.dtype), ("done", (K, self.N), torch.uint8),
+                 ("term", (K, self.N, self.D), self.dtype), ("reasons", (K, self.N), torch.int16))
+        if given is not None:
+            for (what, shape, dtype), t in zip(specs, given):
+                self._out(t, shape, dtype, what)
+            return given
+        return tuple(self._new(*shape, dtype=dtype) if want else None
+                     for (_, shape, dtype), want in zip(specs, (True, True, True, want_terminal, want_reasons)))
+
     def rollout_into(self, nsteps: int, actions, obs, rew, done, term=None, reasons=None):
         """Allocation-free variant of rollout() writing into caller tensors ([K,N,...]); shapes, dtypes, device and
         contiguity are checked (the library takes addresses: a wrong K or dtype would write out of bounds)."""
@@ -272,11 +154,7 @@ class HipSim:
         if obs is None or rew is None or done is None:
             raise ValueError("rollout_into: obs, rew and done are required")
         self._out(actions, (K, self.N, 2), self.dtype, "actions")
-        self._out(obs, (K, self.N, self.D), self.dtype, "obs")
-        self._out(rew, (K, self.N), self.dtype, "rew")
-        self._out(done, (K, self.N), torch.uint8, "done")
-        self._out(term, (K, self.N, self.D), self.dtype, "term")
-        self._out(reasons, (K, self.N), torch.int16, "reasons")
+        self._steps_out(K, given=(obs, rew, done, term, reasons))
         self._check(self._lib.os2r_rollout(self._h, int(nsteps), _ptr(actions), _ptr(obs), _ptr(rew), _ptr(done), _ptr(term),
                                            _ptr(reasons), self._stream()), "os2r_rollout")
 
@@ -297,6 +175,33 @@ class HipSim:
             return sigma.contiguous(), 0
         return sigma.t().contiguous(), abi.POLICY_SIGMA_PER_ENV      # the kernel's layout: [2][N], env index fastest
 
+    def _noise_args(self, name, sigma, salt, **wants):
+        """sigma and salt of rollout_policy / rollout_schedule (`name`) -> (sigma tensor or None, its flag bits, salt), checked;
+        `wants` are the outputs that exist only with sigma."""
+        if sigma is None and (any(wants.values()) or salt):
+            raise ValueError(f"{name}: {', '.join(wants)} and salt need sigma (sigma=0.0: the deterministic policy)")
+        if not 0 <= int(salt) < 2 ** 32:
+            raise ValueError(f"{name}: salt must be a 32-bit unsigned value")
+        return ((None, 0) if sigma is None else self._sigma(sigma)) + (int(salt),)
+
+    def _policy_weights(self, name, weights, table):
+        """weights of rollout_policy ([2, D+1], or one set per environment [N, 2, D+1]) or, `table`, of rollout_schedule (the
+        same behind a T: [T, 2, D+1] or [N, T, 2, D+1]) -> (contiguous tensor in the kernel's layout, the per-env flag bit, T)."""
+        R = self.D + 1
+        if not isinstance(weights, torch.Tensor):
+            weights = torch.as_tensor(weights)
+        shape = tuple(weights.shape)
+        lead = shape[:-2]                          # what stands before the [2, D+1] of one set: (), (N,), (T,) or (N, T)
+        per_env = len(lead) == 1 + table and lead[0] == self.N
+        T = lead[-1] if table and lead else 1
+        if shape[-2:] != (2, R) or len(lead) != table + per_env or T < 1:
+            want = f"[T, 2, {R}] or [{self.N}, T, 2, {R}] with T >= 1" if table else f"[2, {R}] or [{self.N}, 2, {R}]"
+            raise ValueError(f"{name}: weights must be {want}, got {shape}")
+        if weights.dtype != self.dtype or weights.device != self.device:
+            raise ValueError(f"{name}: weights must be {self.dtype} on {self.device}, got {weights.dtype} on {weights.device}")
+        # the kernel's layout per environment: [T][2][D+1][N], env index fastest
+        return (weights.movedim(0, -1) if per_env else weights).contiguous(), abi.POLICY_PER_ENV if per_env else 0, T
+
     def rollout_policy(self, nsteps: int, weights, *, tanh: bool = False, first_episode: bool = False, want_outputs: bool = False,
                        want_terminal: bool = False, want_reasons: bool = False, sigma=None, salt: int = 0,
                        want_actions: bool = False, want_noise: bool = False):
@@ -313,43 +218,22 @@ class HipSim:
         K = int(nsteps)
         if K < 1:
             raise ValueError("rollout_policy: nsteps must be >= 1")
-        if sigma is None and (want_actions or want_noise or salt):
-            raise ValueError("rollout_policy: want_actions, want_noise and salt need sigma (sigma=0.0: the deterministic policy)")
-        if not 0 <= int(salt) < 2 ** 32:
-            raise ValueError("rollout_policy: salt must be a 32-bit unsigned value")
-        sg, sg_flags = (None, 0) if sigma is None else self._sigma(sigma)
-        R = self.D + 1
-        if not isinstance(weights, torch.Tensor):
-            weights = torch.as_tensor(weights)
-        shape = tuple(weights.shape)
-        flags = (abi.POLICY_TANH if tanh else 0) | (abi.POLICY_FIRST_EPISODE if first_episode else 0)
-        if shape == (2, R):
-            w = weights
-        elif shape == (self.N, 2, R):
-            w = weights.permute(1, 2, 0)                  # the kernel's layout: [2][D+1][N], env index fastest
-            flags |= abi.POLICY_PER_ENV
-        else:
-            raise ValueError(f"rollout_policy: weights must be [2, {R}] or [{self.N}, 2, {R}], got {shape}")
-        if weights.dtype != self.dtype or weights.device != self.device:
-            raise ValueError(f"rollout_policy: weights must be {self.dtype} on {self.device}, got {weights.dtype} on {weights.device}")
-        w = w.contiguous()
+        sg, sg_flags, salt = self._noise_args("rollout_policy", sigma, salt, want_actions=want_actions, want_noise=want_noise)
+        w, per_env, _ = self._policy_weights("rollout_policy", weights, table=False)
+        flags = (abi.POLICY_TANH if tanh else 0) | (abi.POLICY_FIRST_EPISODE if first_episode else 0) | per_env
         ret, length = self._new(self.N), self._new(self.N, dtype=torch.int32)
-        obs = rew = done = term = why = None
-        if want_outputs:
-            obs, rew = self._new(K, self.N, self.D), self._new(K, self.N)
-            done = self._new(K, self.N, dtype=torch.uint8)
-            term = self._new(K, self.N, self.D) if want_terminal else None
-            why = self._new(K, self.N, dtype=torch.int16) if want_reasons else None
+        outs = self._steps_out(K, want_terminal, want_reasons) if want_outputs else (None,) * 5
+        obs, rew, done, term, why = outs
         if sg is not None:
             act = self._new(K, self.N, 2) if want_actions else None
             eps = self._new(K, self.N, 2) if want_noise else None
-            self._check(self._lib.os2r_rollout_policy_noisy(self._h, K, _ptr(w), flags | sg_flags, _ptr(sg), int(salt), _ptr(ret),
+            self._check(self._lib.os2r_rollout_policy_noisy(self._h, K, _ptr(w), flags | sg_flags, _ptr(sg), salt, _ptr(ret),
                                                             _ptr(length), _ptr(obs), _ptr(rew), _ptr(done), _ptr(term), _ptr(why),
                                                             _ptr(act), _ptr(eps), self._stream()), "os2r_rollout_policy_noisy")
-            return ret, length, ((obs, rew, done, term, why) if want_outputs else None), (act, eps)
+            return ret, length, (outs if want_outputs else None), (act, eps)
         self._check(self._lib.os2r_rollout_policy(self._h, K, _ptr(w), flags, _ptr(ret), _ptr(length), _ptr(obs), _ptr(rew),
                                                   _ptr(done), _ptr(term), _ptr(why), self._stream()), "os2r_rollout_policy")
-        return ret, length, ((obs, rew, done, term, why) if want_outputs else None)
+        return ret, length, (outs if want_outputs else None)
 
     def rollout_schedule(self, nsteps: int, weights, *, clock: str = "window", wrap: bool = False, first_slot: int = 0,
                          tanh: bool = False, first_episode: bool = False, sigma=None, salt: int = 0, want_outputs: bool = False,
@@ -373,43 +257,20 @@ class HipSim:
             raise ValueError(f"rollout_schedule: clock must be 'window' or 'episode', got {clock!r}")
         if not 0 <= int(first_slot) < 2 ** 31:
             raise ValueError("rollout_schedule: first_slot must be a non-negative 32-bit value")
-        if sigma is None and (want_noise or salt):
-            raise ValueError("rollout_schedule: want_noise and salt need sigma (sigma=0.0: the deterministic policy)")
-        if not 0 <= int(salt) < 2 ** 32:
-            raise ValueError("rollout_schedule: salt must be a 32-bit unsigned value")
-        sg, sg_flags = (None, 0) if sigma is None else self._sigma(sigma)
-        R = self.D + 1
-        if not isinstance(weights, torch.Tensor):
-            weights = torch.as_tensor(weights)
-        shape = tuple(weights.shape)
-        flags = ((abi.POLICY_TANH if tanh else 0) | (abi.POLICY_FIRST_EPISODE if first_episode else 0) |
+        sg, sg_flags, salt = self._noise_args("rollout_schedule", sigma, salt, want_noise=want_noise)
+        w, per_env, T = self._policy_weights("rollout_schedule", weights, table=True)
+        flags = ((abi.POLICY_TANH if tanh else 0) | (abi.POLICY_FIRST_EPISODE if first_episode else 0) | per_env |
                  (abi.POLICY_CLOCK_EPISODE if clock == "episode" else 0) | (abi.POLICY_SCHEDULE_WRAP if wrap else 0))
-        if len(shape) == 3 and shape[0] >= 1 and shape[1:] == (2, R):
-            T, w = shape[0], weights
-        elif len(shape) == 4 and shape[0] == self.N and shape[1] >= 1 and shape[2:] == (2, R):
-            T, w = shape[1], weights.permute(1, 2, 3, 0)      # the kernel's layout: [T][2][D+1][N], env index fastest
-            flags |= abi.POLICY_PER_ENV
-        else:
-            raise ValueError(f"rollout_schedule: weights must be [T, 2, {R}] or [{self.N}, T, 2, {R}] with T >= 1, got {shape}")
-        if weights.dtype != self.dtype or weights.device != self.device:
-            raise ValueError(f"rollout_schedule: weights must be {self.dtype} on {self.device}, got {weights.dtype} on {weights.device}")
-        w = w.contiguous()
         ret, length = self._new(self.N), self._new(self.N, dtype=torch.int32)
-        obs = rew = done = term = why = None
-        if want_outputs:
-            obs, rew = self._new(K, self.N, self.D), self._new(K, self.N)
-            done = self._new(K, self.N, dtype=torch.uint8)
-            term = self._new(K, self.N, self.D) if want_terminal else None
-            why = self._new(K, self.N, dtype=torch.int16) if want_reasons else None
+        outs = self._steps_out(K, want_terminal, want_reasons) if want_outputs else (None,) * 5
+        obs, rew, done, term, why = outs
         act = self._new(K, self.N, 2) if want_actions else None
         eps = self._new(K, self.N, 2) if want_noise else None
-        fn = getattr(self._lib, "os2r_rollout_policy_scheduled", None)
-        if fn is None:
-            raise Os2rError("this libos2r.so has no os2r_rollout_policy_scheduled")
-        self._check(fn(self._h, K, _ptr(w), T, int(first_slot), flags | sg_flags, _ptr(sg), int(salt), _ptr(ret), _ptr(length),
-                       _ptr(obs), _ptr(rew), _ptr(done), _ptr(term), _ptr(why), _ptr(act), _ptr(eps), self._stream()),
+        self._check(self._lib.os2r_rollout_policy_scheduled(self._h, K, _ptr(w), T, int(first_slot), flags | sg_flags, _ptr(sg), salt,
+                                                            _ptr(ret), _ptr(length), _ptr(obs), _ptr(rew), _ptr(done), _ptr(term),
+                                                            _ptr(why), _ptr(act), _ptr(eps), self._stream()),
                     "os2r_rollout_policy_scheduled")
-        return ret, length, ((obs, rew, done, term, why) if want_outputs else None), (act, eps)
+        return ret, length, (outs if want_outputs else None), (act, eps)
 
     def reset(self, mask: Optional[torch.Tensor] = None):
         m = None if mask is None else self._in(mask, (self.N,), torch.uint8)
@@ -442,13 +303,9 @@ class HipSim:
     def bench_enqueue_shards(sims, streams, nsteps: int):
         """Enqueue nsteps random-action steps of every shard `sims[i]` on `streams[i]` (torch streams), round robin and
         without waiting (include/os2r.h: os2r_bench_steps_multi): all the streams start together."""
-        lib = sims[0]._lib
-        if isinstance(lib, _PybindLib):
-            rc = lib.m.bench_steps_multi([lib._a(s._h) for s in sims], [int(st.cuda_stream) for st in streams], int(nsteps))
-        else:
-            hs = (C.c_void_p * len(sims))(*[s._h for s in sims])
-            sts = (C.c_void_p * len(sims))(*[C.c_void_p(st.cuda_stream) for st in streams])
-            rc = lib.os2r_bench_steps_multi(hs, sts, len(sims), int(nsteps))
+        hs = (C.c_void_p * len(sims))(*[s._h for s in sims])
+        sts = (C.c_void_p * len(sims))(*[C.c_void_p(st.cuda_stream) for st in streams])
+        rc = sims[0]._lib.os2r_bench_steps_multi(hs, sts, len(sims), int(nsteps))
         sims[0]._check(rc, "os2r_bench_steps_multi")
 
     WORK_COUNTERS = ("wave_iterations", "scanned_bodies", "row_bodies", "body_sweeps", "sweeps", "lane_contacts",
@@ -718,11 +575,8 @@ class HipSim:
             actions = obs = None
         if B is None:
             raise ValueError("lqr_gains: B is required")
-        fn = getattr(self._lib, "os2r_lqr_gains", None)
-        if fn is None:
-            raise Os2rError("this libos2r.so has no os2r_lqr_gains")
-        self._check(fn(self._h, K, M, sweeps, _ptr(A), _ptr(B), q, r, _ptr(P_final), _ptr(gains_out), _ptr(P_out), _ptr(flags_out),
-                       _ptr(actions), _ptr(obs), _ptr(weights_out), self._stream()), "os2r_lqr_gains")
+        self._check(self._lib.os2r_lqr_gains(self._h, K, M, sweeps, _ptr(A), _ptr(B), q, r, _ptr(P_final), _ptr(gains_out), _ptr(P_out),
+                                             _ptr(flags_out), _ptr(actions), _ptr(obs), _ptr(weights_out), self._stream()), "os2r_lqr_gains")
 
     def lqr_gains(self, A, B, Q, R, *, knots: int = 1, sweeps: int = 1, P_final=None, actions=None, obs=None, want_gains: bool = True,
                   want_P: bool = False, want_flags: bool = True, want_weights: bool = False):
@@ -789,4 +643,4 @@ class HipSim:
 
     @step_count.setter
     def step_count(self, value: int):
-        self._check(self._lib.os2r_set_step_count(self._h, C.c_uint64(int(value))), "os2r_set_step_count")
+        self._check(self._lib.os2r_set_step_count(self._h, int(value)), "os2r_set_step_count")
