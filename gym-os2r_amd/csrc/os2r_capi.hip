@@ -36,7 +36,16 @@ struct JitEntry {
   hipFunction_t fn_layout[2] = {};
   unsigned long long layout_kinds = 0, layout_srcs = 0;
   int layout_dim = -1;
+  // optional, usually code objects of their own (csrc/os2r_jit_fused_unit.hip), by per-env parameters: the fused rollout and the
+  // fused policy rollout (contact, default solver; os2r_jit_rollout_c1_d*, os2r_jit_policy_c1_d*) ...
+  hipFunction_t fn_rollout[2] = {}, fn_policy[2] = {};
+  // ... built for the observation layout below if the object announces one (fused_dim >= 0), else for any layout
+  unsigned long long fused_kinds = 0, fused_srcs = 0;
+  int fused_dim = -1;
+  // os2r_jit_lin_c*_d* (_s): [contact][per-env parameters][default sweep counts compiled in], as fn
+  hipFunction_t fn_lin[2][2][2] = {};
 };
+enum JitKind { kJitStep, kJitRollout, kJitPolicy, kJitLin };
 
 static void task_layout(const Os2rTaskSpec& t, unsigned long long& kinds, unsigned long long& srcs, int& dim) {
   kinds = 0; srcs = 0; dim = t.obs_dim;
@@ -49,21 +58,34 @@ static void task_layout(const Os2rTaskSpec& t, unsigned long long& kinds, unsign
 static std::mutex g_jit_mutex;
 static std::deque<JitEntry> g_jit;   // entries are never removed: handles keep pointers into it
 
-// newest registration of this robot that exports kernels for the handle's contact flag (a robot may have been
-// registered once with and once without ground contact: two code objects)
-static const JitEntry* find_jit(const Os2rModel& m, int dtype, int device, bool contact, const Os2rTaskSpec& task) {
+// newest registration of this robot that exports kernels of this kind for the handle's contact flag (a robot may have been
+// registered once with and once without ground contact, and every kind is a code object of its own)
+static const JitEntry* find_jit(const Os2rModel& m, int dtype, int device, bool contact, const Os2rTaskSpec& task, JitKind kind = kJitStep) {
   unsigned long long kinds, srcs;
   int dim;
   task_layout(task, kinds, srcs, dim);
   std::lock_guard<std::mutex> lock(g_jit_mutex);
   const JitEntry* any = nullptr;
-  for (auto it = g_jit.rbegin(); it != g_jit.rend(); ++it)
-    if (it->dtype == dtype && it->device == device && (it->fn[contact][0][0] || it->fn[contact][1][0]) &&
-        os2r::same_model(it->model, m)) {
-      // a code object built for this handle's observation layout is preferred over a newer one built for another
-      if (contact && it->layout_dim == dim && it->layout_kinds == kinds && it->layout_srcs == srcs) return &*it;
-      if (!any) any = &*it;
+  for (auto it = g_jit.rbegin(); it != g_jit.rend(); ++it) {
+    if (it->dtype != dtype || it->device != device) continue;
+    bool exports = false, mine = false;   // mine: built for this handle's observation layout
+    if (kind == kJitStep) {
+      exports = it->fn[contact][0][0] || it->fn[contact][1][0];
+      mine = contact && it->layout_dim == dim && it->layout_kinds == kinds && it->layout_srcs == srcs;
+    } else if (kind == kJitLin) {
+      exports = it->fn_lin[contact][0][0] || it->fn_lin[contact][0][1] || it->fn_lin[contact][1][0] || it->fn_lin[contact][1][1];
+      mine = true;   // (no epilogue, no layout)
+    } else {
+      const hipFunction_t* f = kind == kJitRollout ? it->fn_rollout : it->fn_policy;
+      mine = it->fused_dim == dim && it->fused_kinds == kinds && it->fused_srcs == srcs;
+      // a fused kernel with another task's layout folded in cannot serve this handle at all
+      exports = contact && (f[0] || f[1]) && (it->fused_dim < 0 || mine);
     }
+    if (!exports || !os2r::same_model(it->model, m)) continue;
+    // a code object built for this handle's observation layout is preferred over a newer one built for another
+    if (mine) return &*it;
+    if (!any) any = &*it;
+  }
   return any;
 }
 
@@ -91,6 +113,8 @@ struct SimBase {
   unsigned cmask = 0;
   int model_id = -1;  // matching constexpr model table, -1: run-time model kernels
   const JitEntry* jit = nullptr;  // registered model-specialised code object (os2r_register_model_kernels)
+  // with it, where registered: the robot's fused rollout, fused policy rollout and linearize kernels (resolved at creation too)
+  const JitEntry *jit_rollout = nullptr, *jit_policy = nullptr, *jit_lin = nullptr;
   bool dr = false;
   size_t esz = 8;
   unsigned long long step_count = 0;
@@ -332,6 +356,26 @@ int do_reset(Os2rSim* s, const uint8_t* mask, void* obs, hipStream_t st) {
   return OS2R_OK;
 }
 
+// A kernel of a registered code object: one wave per 64 environments (times grid_y), `args` as the kernel-argument buffer
+template <typename Args>
+hipError_t jit_launch(hipFunction_t fn, const Args& a, long long N, unsigned grid_y, hipStream_t st) {
+  Args args = a;
+  size_t size = sizeof(args);
+  void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &args, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
+  return hipModuleLaunchKernel(fn, (unsigned)((N + kWave - 1) / kWave), grid_y, 1, kWave, 1, 1, 0, st, nullptr, extra);
+}
+
+// The fused kernel of a handle with a code object, out of fn_rollout / fn_policy of the entry resolved at creation: under the
+// conditions the compiled-in robots have a fused variant (ground contact, default solver, no work counters), for the handle's
+// per-env-parameter flag as it is now (os2r_set_params and os2r_copy_envs can switch it on); null: the launch loop
+template <typename T>
+hipFunction_t jit_fused_fn(const Os2rSim* s, const hipFunction_t* by_dr) {
+  if (!s->jit || !by_dr || s->counters || !(s->cfg.contact != 0 && s->cmask != 0u)) return nullptr;
+  const int exact = s->cfg.pgs_normal_iters > 0 ? s->cfg.pgs_exact : 0;   // (as make_args)
+  if (!is_std_solver<T>(s->cfg.pgs_iters, s->cfg.pgs_normal_iters, exact, s->cfg.model.nq)) return nullptr;
+  return by_dr[s->dr];
+}
+
 template <typename T>
 int do_step(Os2rSim* s, const void* actions, void* obs, void* reward, uint8_t* done, void* term, hipStream_t st) {
   StepArgs<T> a = make_args<T>(s);
@@ -346,11 +390,7 @@ int do_step(Os2rSim* s, const void* actions, void* obs, void* reward, uint8_t* d
   if (a.counters && jit_fn) { s->err = "no counting variant in run-time code objects"; return OS2R_ERR_INVALID; }
   if (jit_fn) {
     // the robot's own code object: same StepArgs, passed as the kernel-argument buffer
-    StepArgs<T> args = a;
-    size_t size = sizeof(args);
-    void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &args, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
-    const unsigned grid = (unsigned)((a.N + kWave - 1) / kWave);
-    HIP_TRY(s, hipModuleLaunchKernel(jit_fn, grid, 1, 1, kWave, 1, 1, 0, st, nullptr, extra));
+    HIP_TRY(s, jit_launch(jit_fn, a, a.N, 1, st));
   } else if (Launcher<T>::step(s->nq, s->model_id, s->cfg.contact != 0, s->dr, a, st) != 0) {
     s->err = a.counters ? "no counting variant of the step kernel for this configuration" : "no step kernel for this chain length / contact mask";
     return OS2R_ERR_INVALID;
@@ -365,13 +405,20 @@ template <typename T>
 int do_rollout(Os2rSim* s, int K, const void* actions, void* obs, void* reward, uint8_t* done, void* term, uint16_t* reason,
                hipStream_t st) {
   const size_t N = (size_t)s->cfg.num_envs, D = (size_t)s->D;
-  if (!s->jit && !s->counters) {
+  const hipFunction_t jit_fn = jit_fused_fn<T>(s, s->jit_rollout ? s->jit_rollout->fn_rollout : nullptr);
+  if ((!s->jit || jit_fn) && !s->counters) {
     StepArgs<T> a = make_args<T>(s);
     a.actions = (const T*)actions; a.obs = (T*)obs; a.reward = (T*)reward; a.done = done; a.term_obs = (T*)term;
     a.reason = reason;
     a.done_mask = nullptr;   // (a rollout writes neither of the per-step buffers set on the handle)
     a.rollout_steps = K;
-    const int rc = Launcher<T>::step(s->nq, s->model_id, s->cfg.contact != 0, s->dr, a, st);
+    int rc;
+    if (jit_fn) {
+      HIP_TRY(s, jit_launch(jit_fn, a, a.N, 1, st));
+      rc = 0;
+    } else {
+      rc = Launcher<T>::step(s->nq, s->model_id, s->cfg.contact != 0, s->dr, a, st);
+    }
     if (rc == 0) {
       HIP_TRY(s, hipGetLastError());
       s->step_count += (unsigned long long)K;
@@ -448,12 +495,14 @@ int do_rollout_policy(Os2rSim* s, int K, const void* w, int flags, void* ret, in
   p.sigma = (const T*)sigma; p.salt = salt; p.act_out = (T*)act_out; p.eps_out = (T*)eps_out;
   // time schedule (os2r_rollout_policy_scheduled): period 0 is the one set of the two entry points above
   p.period = period; p.first_slot = first_slot;
-  if (!s->jit && !s->counters) {
+  const hipFunction_t jit_fn = jit_fused_fn<T>(s, s->jit_policy ? s->jit_policy->fn_policy : nullptr);
+  if ((!s->jit || jit_fn) && !s->counters) {
     p.s = make_args<T>(s);
     p.s.obs = (T*)obs; p.s.reward = (T*)reward; p.s.done = done; p.s.term_obs = (T*)term; p.s.reason = reason;
     p.s.done_mask = nullptr;   // (neither of the per-step buffers set on the handle is written)
     p.s.rollout_steps = K;
-    if (Launcher<T>::policy_rollout(s->model_id, s->cfg.contact != 0, s->dr, p, st) == 0) {
+    if (jit_fn) HIP_TRY(s, jit_launch(jit_fn, p, p.s.N, 1, st));
+    if (jit_fn || Launcher<T>::policy_rollout(s->model_id, s->cfg.contact != 0, s->dr, p, st) == 0) {
       HIP_TRY(s, hipGetLastError());
       s->step_count += (unsigned long long)K;
       return OS2R_OK;
@@ -577,7 +626,20 @@ int do_linearize(Os2rSim* s, const void* actions, const double* eps, void* next,
   if (jac_a) for (int j = 0; j < 2 * nq; ++j) p.col[p.ncols++] = j;
   if (jac_b) for (int j = 0; j < 2; ++j) p.col[p.ncols++] = 2 * nq + j;
   if (next) p.col[p.ncols++] = 2 * nq + 2;
-  if (Launcher<T>::linearize(nq, s->model_id, s->cfg.contact != 0, s->dr, p, st) != 0) {
+  // a handle with a code object: the linearize kernel beside the step kernel do_step picks (the layout variant runs the
+  // substep instantiation of ..._s), where the robot's registrations export it; else the generic kernels
+  hipFunction_t jit_fn = nullptr;
+  if (s->jit && s->jit_lin) {
+    const bool contact = s->cfg.contact != 0 && s->cmask != 0u;
+    const bool std_step = is_std_solver<T>(p.s.pgs_iters, p.s.pgs_normal_iters, p.s.pgs_exact, s->cfg.model.nq) &&
+                          (s->jit->fn[contact][s->dr][1] ||
+                           (contact && s->jit->fn_layout[s->dr] && s->jit->layout_dim == p.s.layout_dim &&
+                            s->jit->layout_kinds == p.s.layout_kinds && s->jit->layout_srcs == p.s.layout_srcs));
+    jit_fn = s->jit_lin->fn_lin[contact][s->dr][std_step];
+  }
+  if (jit_fn) {
+    HIP_TRY(s, jit_launch(jit_fn, p, p.s.N, (unsigned)p.ncols, st));
+  } else if (Launcher<T>::linearize(nq, s->model_id, s->cfg.contact != 0, s->dr, p, st) != 0) {
     s->err = "os2r_linearize: no kernel for this chain length";
     return OS2R_ERR_INVALID;
   }
@@ -699,6 +761,12 @@ int os2r_create(const Os2rConfig* cfg, Os2rSim** out) {
   if (cfg->contact)
     for (int k = 0; k < cfg->model.ncand; ++k) s->cmask |= 1u << cfg->model.cand_body[k];
   if (s->model_id < 0) s->jit = find_jit(cfg->model, cfg->dtype, cfg->device, cfg->contact != 0 && s->cmask != 0u, cfg->task);
+  if (s->jit) {   // the other kinds serve a handle only beside the robot's own step kernels: one arithmetic per handle
+    const bool contact = cfg->contact != 0 && s->cmask != 0u;
+    s->jit_rollout = find_jit(cfg->model, cfg->dtype, cfg->device, contact, cfg->task, kJitRollout);
+    s->jit_policy = find_jit(cfg->model, cfg->dtype, cfg->device, contact, cfg->task, kJitPolicy);
+    s->jit_lin = find_jit(cfg->model, cfg->dtype, cfg->device, contact, cfg->task, kJitLin);
+  }
   int rc = OS2R_OK;
   auto fail = [&](int code) { g_create_error = s->err; free_all(s); delete s; return code; };
   DeviceGuard guard(cfg->device);   // allocate and initialise on the handle's device, then give the caller's back
@@ -989,11 +1057,30 @@ int os2r_register_model_kernels(const Os2rModel* model, int32_t dtype, int32_t d
         if (hipModuleGetFunction(&e.fn[c][d][v], e.module, (name + (v ? "_s" : "")).c_str()) == hipSuccess) ++found;
         else e.fn[c][d][v] = nullptr;
     }
+  int fused = 0;
+  for (int d = 0; d < 2; ++d) {
+    const std::string tail = std::string("_c1_d") + char('0' + d);
+    if (hipModuleGetFunction(&e.fn_rollout[d], e.module, ("os2r_jit_rollout" + tail).c_str()) == hipSuccess) ++fused;
+    else e.fn_rollout[d] = nullptr;
+    if (hipModuleGetFunction(&e.fn_policy[d], e.module, ("os2r_jit_policy" + tail).c_str()) == hipSuccess) ++fused;
+    else e.fn_policy[d] = nullptr;
+    for (int c = 0; c < 2; ++c)
+      for (int v = 0; v < 2; ++v) {
+        const std::string name = std::string("os2r_jit_lin_c") + char('0' + c) + "_d" + char('0' + d) + (v ? "_s" : "");
+        if (hipModuleGetFunction(&e.fn_lin[c][d][v], e.module, name.c_str()) == hipSuccess) ++found;
+        else e.fn_lin[c][d][v] = nullptr;
+      }
+  }
+  found += fused;
   hipDeviceptr_t lay = nullptr;
   size_t lay_bytes = 0;
   if (hipModuleGetGlobal(&lay, &lay_bytes, e.module, "os2r_jit_layout") == hipSuccess && lay_bytes >= 3 * sizeof(unsigned long long)) {
     unsigned long long v[3] = {};
-    if (hipMemcpy(v, lay, sizeof(v), hipMemcpyDeviceToHost) == hipSuccess) {
+    const bool read = hipMemcpy(v, lay, sizeof(v), hipMemcpyDeviceToHost) == hipSuccess;
+    // an object that announces a layout has it folded into its fused kernels: one that cannot be read serves no handle
+    if (read) { e.fused_kinds = v[0]; e.fused_srcs = v[1]; e.fused_dim = (int)v[2]; }
+    else if (fused) { found -= fused; for (int d = 0; d < 2; ++d) e.fn_rollout[d] = e.fn_policy[d] = nullptr; }
+    if (read) {
       bool both = true;
       for (int d = 0; d < 2; ++d)
         if (hipModuleGetFunction(&e.fn_layout[d], e.module, (std::string("os2r_jit_step_c1_d") + char('0' + d) + "_l").c_str()) != hipSuccess) { e.fn_layout[d] = nullptr; both = false; }
@@ -1001,7 +1088,7 @@ int os2r_register_model_kernels(const Os2rModel* model, int32_t dtype, int32_t d
     }
   }
   (void)hipGetLastError();   // a missing variant is not an error
-  if (!found) { (void)hipModuleUnload(e.module); g_create_error = std::string(path) + " exports no os2r_jit_step_* kernel"; return OS2R_ERR_INVALID; }
+  if (!found) { (void)hipModuleUnload(e.module); g_create_error = std::string(path) + " exports no os2r_jit_* kernel this library knows"; return OS2R_ERR_INVALID; }
   std::lock_guard<std::mutex> lock(g_jit_mutex);
   g_jit.push_back(e);
   return OS2R_OK;

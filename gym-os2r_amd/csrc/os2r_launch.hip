@@ -65,7 +65,7 @@ int Launcher<T>::policy_rollout(int model_id, bool contact, bool dr, const Polic
     case 1: return policy_rollout_unit<T, 1>(contact, dr, a, s);
     case 2: return policy_rollout_unit<T, 2>(contact, dr, a, s);
     case 3: return policy_rollout_unit<T, 3>(contact, dr, a, s);
-    default: return 2;   // run-time models: no fused variant
+    default: return 2;   // run-time models: no fused variant here (a robot's own one is in its code objects: os2r_capi.hip)
   }
 }
 template <typename T>

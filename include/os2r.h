@@ -346,6 +346,19 @@ OS2R_API int os2r_rollout_policy_scheduled(Os2rSim* sim, int nsteps, const void*
  * symbol os2r_jit_layout = {kinds, sources, slots} (4 bits per observation slot): the contact
  * kernels with that observation layout folded in; handles whose task has exactly that layout use
  * them, and of several code objects of one robot the one built for the handle's layout is taken.
+ * Further optional kernels, each in the step object or (as jit.py builds them, from
+ * gym-os2r_amd/csrc/os2r_jit_fused_unit.hip) in a code object of its own registered by a call of
+ * its own; a handle takes them only beside step kernels of the same robot:
+ *   os2r_jit_rollout_c1_d{0,1}       os2r_rollout in one launch (argument: the step kernels')
+ *   os2r_jit_policy_c1_d{0,1}        the three os2r_rollout_policy entry points in one launch
+ *   os2r_jit_lin_c{0,1}_d{0,1}[_s]   os2r_linearize on the robot's own arithmetic; _s beside the
+ *                                    step kernels' _s (default sweep counts compiled in)
+ * The first two serve handles with ground contact, the default solver settings and no work
+ * counters -- where the compiled-in robots have a fused variant; every other handle keeps its
+ * launch loop.  If their object carries os2r_jit_layout they have that layout folded in and
+ * serve handles of that layout only; without the symbol they serve any layout.  An object is
+ * accepted if it exports at least one kernel named in this comment.  A handle keeps what was
+ * registered when it was created.
  * Errors: os2r_last_error(NULL).                                                            */
 OS2R_API int os2r_model_is_compiled_in(const Os2rModel* model);
 OS2R_API int os2r_register_model_kernels(const Os2rModel* model, int32_t dtype, int32_t device,
@@ -446,10 +459,11 @@ OS2R_API int os2r_copy_envs(Os2rSim* dst, Os2rSim* src, const int32_t* index_dev
  * its mirror, the done-reason / done-mask buffers and the work counters are as they were.  Stream-ordered on `stream`, no
  * host synchronisation, no allocation, no buffer of the handle's.
  * Contract: every f(.) above equals, bit for bit, what os2r_step leaves in os2r_get_state when started from that point, the
- * same solver state, the same parameters and that action, for every configuration os2r_create accepts.  Exception: for a
- * robot that runs a registered code object (os2r_register_model_kernels) this call uses the generic run-time-model kernels
- * of the library; the equality then holds against those (a handle created without the registration, OS2R_JIT=0 in the
- * Python package), not against the robot's own code object, which exports no linearise kernel.
+ * same solver state, the same parameters and that action, for every configuration os2r_create accepts.  For a robot that
+ * runs a registered code object (os2r_register_model_kernels) that holds against the robot's own step kernels whenever its
+ * registrations export the matching os2r_jit_lin_* kernel (gym_os2r_amd/jit.py builds them all).  Only where they do not
+ * -- an object built by hand without them, OS2R_JIT_FUSED=0 in the Python package -- this call runs the generic
+ * run-time-model kernels of the library, and the equality holds against those (a handle created without any registration).
  * A quotient whose two evaluations end in different contact modes is the secant across the kink: eps is the caller's tool,
  * the library does not judge it.
  * Errors: OS2R_ERR_INVALID for a null handle (os2r_last_error(NULL)), null actions_dev, null eps, all outputs null, an eps
