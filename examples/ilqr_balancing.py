@@ -1,0 +1,156 @@
+#!/usr/bin/env python3
+"""iLQR on Monopod-nonorm-balance-v1 with every piece of an iteration on the device: M trajectories of K knots are optimised side
+by side towards a target posture, the backward pass in one os2rc_ilqr_backward launch.
+
+  python examples/ilqr_balancing.py [--envs 64] [--steps 40] [--iters 10] [--settle 300] [--perturb 0.05] [--mu 0.0] [--eps 1e-4]
+
+The cost of a trajectory is sum_k 1/2 (x_k - x*)'Q(x_k - x*) + 1/2 a_k'R a_k plus 1/2 (x_K - x*)'Q(x_K - x*), read off the raw
+observation slots (state components the task does not observe carry no weight); x* is the posture the PD of lqr_balancing.py
+settles in, the starts are that posture perturbed, the first nominal is zero torque.  Each iteration:
+  1. the nominal is replayed from the start and knot k of trajectory m forked into lane k M + m of a K M-lane handle
+     (copy_envs_from, one launch per knot);
+  2. one os2r_linearize launch returns A_k, B_k of every knot;
+  3. lx = Q (x_k - x*), lu = R a_k and p_final = Q (x_K - x*) are formed in torch;
+  4. one ilqr_backward launch returns the refusal flags, the two terms of the expected cost change and ONE table of weights
+     for the step sizes 1, 1/2, 1/4, 1/8;
+  5. one rollout_schedule launch on a handle of 4 M environments, forked from knot 0, runs all four candidates of every
+     trajectory with the table as it came;
+  6. their costs are read off the returned observations and actions;
+  7. the best step size that lowers the summed cost is accepted (its applied actions are the new nominal); if none does, mu is
+     raised and the iteration repeated.
+Printed per iteration: the cost (mean over the trajectories), the step size, mu, the refused knots, and the predicted against
+the actual change.  The script prints what happened; it claims no control quality: a quotient across a change of contact mode
+is a secant, the default eps is not tuned, and the actions saturate, which the model knows nothing about.
+"""
+import argparse
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+
+import gym_os2r_amd as g
+from gym_os2r_amd.control import slot_columns
+from lqr_balancing import weights_of_gain
+
+ALPHAS = (1.0, 0.5, 0.25, 0.125)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--envs", type=int, default=64, help="M: trajectories optimised side by side")
+    ap.add_argument("--steps", type=int, default=40, help="K: knots (env-steps) of a trajectory")
+    ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--settle", type=int, default=300, help="env-steps under the PD before the target posture is read")
+    ap.add_argument("--perturb", type=float, default=0.05, help="standard deviation of the start perturbation [rad, rad/s]")
+    ap.add_argument("--mu", type=float, default=0.0, help="initial control-space regularisation")
+    ap.add_argument("--eps", type=float, default=None, help="finite-difference step (default: HipSim.linearize's)")
+    ap.add_argument("--kp", type=float, default=8.0)
+    ap.add_argument("--kd", type=float, default=0.15)
+    ap.add_argument("--seed", type=int, default=0)
+    args = ap.parse_args()
+    M, K, nal = args.envs, args.steps, len(ALPHAS)
+    # one task, three handles: the nominal (M trajectories), the knots (K M lanes, knot-major), the candidates (4 M environments)
+    envs = [g.make("Monopod-nonorm-balance-v1", num_envs=n, seed=args.seed) for n in (M, K * M, nal * M)]
+    for e in envs:
+        e.reset()
+    nom, knots, cand = (e.sim for e in envs)
+    dev, dt, nq, D = nom.device, nom.dtype, nom.nq, nom.D
+    n = 2 * nq
+    cols = slot_columns(nom.cfg.task, nq)
+    slots = [d for d in range(D) if cols[d] >= 0]                                     # the raw slots and the state column each shows
+    shown = [cols[d] for d in slots]
+    ih, ik = envs[0].model["act_dof"]
+    print(f"iLQR on Monopod-nonorm-balance-v1: {M} trajectories of {K} knots, nq {nq}, unobserved state columns "
+          f"{sorted(set(range(n)) - set(shown))}, step sizes {ALPHAS}", flush=True)
+
+    # the target posture: where the posture PD settles; the starts: that posture, perturbed on the observed components
+    obs0 = nom.copy_envs_from(nom, want_obs=True)
+    K_pd = torch.zeros(M, 2, n, dtype=dt, device=dev)
+    for j, dof in enumerate((ih, ik)):
+        K_pd[:, j, dof] = args.kp / 2.5
+        K_pd[:, j, nq + dof] = args.kd / 2.5
+    nom.rollout_policy(args.settle, weights_of_gain(K_pd, torch.zeros(M, 2, dtype=dt, device=dev), obs0, cols))
+    target = nom.copy_envs_from(nom, want_obs=True)[:, slots]                         # [M, raw slots]
+    q, qd = nom.get_state()
+    gen = torch.Generator(device=dev).manual_seed(args.seed + 1)
+    observed = torch.tensor([c in shown for c in range(n)], dtype=dt, device=dev)
+    noise = args.perturb * torch.randn(n, M, dtype=dt, device=dev, generator=gen) * observed[:, None]
+    nom.set_state(q + noise[:nq], qd + noise[nq:])
+    start = nom.checkpoint()
+
+    qdiag = torch.tensor([0.0 if c not in shown else (1.0 if c < nq else 0.01) for c in range(n)], dtype=dt, device=dev)
+    Q, R = torch.diag(qdiag), 0.1 * torch.eye(2, dtype=dt, device=dev)
+    qs = qdiag[shown]
+
+    def cost(obs_seq, act):
+        """obs_seq [K+1, B, D] (the knots and the end), act [K, B, 2] -> [B]; B is a multiple of M"""
+        err = obs_seq[:, :, slots] - target.repeat(obs_seq.shape[1] // M, 1)
+        a = act.clamp(-1.0, 1.0)
+        return 0.5 * (err * err * qs).sum(dim=(0, 2)) + 0.5 * torch.einsum("kbi,ij,kbj->b", a, R, a)
+
+    lanes = torch.arange(K * M, dtype=torch.int32, device=dev)
+    fork = [torch.where(lanes // M == k, lanes % M, -1).to(torch.int32) for k in range(K)]   # (a negative entry keeps the lane)
+    first = torch.arange(M, dtype=torch.int32, device=dev).repeat(nal)                # knot 0 of trajectory m, once per step size
+    U = torch.zeros(K, M, 2, dtype=dt, device=dev)
+    mu, it, tries, shown_cost = args.mu, 0, 0, None
+    while it < args.iters and tries < 4 * args.iters:
+        tries += 1
+        # 1. replay the nominal, fork the knots
+        nom.restore(start)
+        ended = 0
+        for k in range(K):
+            knots.copy_envs_from(nom, fork[k])
+            _, _, done, _ = nom.step(U[k], want_terminal=False)
+            ended += int((done != 0).sum())
+        end_obs = nom.copy_envs_from(nom, want_obs=True)
+        obs_k = knots.copy_envs_from(knots, want_obs=True)                            # [K M, D]: the observation at each knot
+        J = cost(torch.cat([obs_k.view(K, M, D), end_obs[None]]), U)
+        if shown_cost is None:
+            shown_cost = float(J.mean())
+            print(f"iter {0:2d} cost {shown_cost:.6e} (the nominal: zero torque; {ended} episode ends inside it)", flush=True)
+        # 2. every knot's Jacobians in one launch
+        a_k = U.reshape(K * M, 2)
+        _, _, A, B = knots.linearize(a_k, args.eps, want_next=False)
+        # 3. the cost's gradients at the knots and behind the last one
+        lx = torch.zeros(K * M, n, dtype=dt, device=dev)
+        lx[:, shown] = qs * (obs_k[:, slots] - target.repeat(K, 1))
+        lu = a_k.clamp(-1.0, 1.0) @ R
+        p_final = torch.zeros(M, n, dtype=dt, device=dev)
+        p_final[:, shown] = qs * (end_obs[:, slots] - target)
+        # 4. the backward pass and the candidates' table in one launch
+        _, _, _, _, flags, dv, table = nom.ilqr_backward(A, B, Q.cpu(), R.cpu(), knots=K, lx=lx, lu=lu, mu=mu, p_final=p_final, actions=a_k,
+                                                         obs=obs_k, alphas=ALPHAS, want_gains=False, want_ff=False, want_weights=True)
+        refused = int(flags.sum())
+        # 5. all candidates of all trajectories in one launch, from knot 0
+        cand.copy_envs_from(knots, first)
+        _, _, (o_c, _, d_c, _, _), (a_c, _) = cand.rollout_schedule(K, table, want_outputs=True, want_actions=True)
+        # 6. their costs
+        J_c = cost(torch.cat([obs_k[:M].repeat(nal, 1)[None], o_c]), a_c).view(nal, M)
+        # 7. the best step size that lowers the summed cost, or more regularisation
+        total = J_c.sum(1)
+        best = int(total.argmin())
+        if float(total[best]) < float(J.sum()):
+            it += 1
+            alpha = ALPHAS[best]
+            predicted = float((alpha * dv[:, :, 0].sum(0) + alpha ** 2 * dv[:, :, 1].sum(0)).mean())
+            actual = float((J_c[best] - J).mean())
+            shown_cost = float(J_c[best].mean())
+            print(f"iter {it:2d} cost {shown_cost:.6e} alpha {alpha:5.3f} mu {mu:.3e} refused {refused} of {K * M} knots, predicted change "
+                  f"{predicted:+.4e} actual {actual:+.4e}; {int((d_c.view(K, nal, M)[:, best] != 0).any(0).sum())} of {M} episodes ended",
+                  flush=True)
+            U = a_c.view(K, nal, M, 2)[:, best].contiguous()
+            mu = 0.5 * mu if mu > 1e-3 else 0.0
+        else:
+            print(f"        no step size lowers the cost at mu {mu:.3e} (best alpha {ALPHAS[best]}: {float(total[best] - J.sum()) / M:+.4e}, "
+                  f"refused {refused} of {K * M} knots): mu raised", flush=True)
+            mu = max(10.0 * mu, 0.1)
+    while it < args.iters:                                                            # (kept: every iteration has its line)
+        it += 1
+        print(f"iter {it:2d} cost {shown_cost:.6e} (no step size was accepted)", flush=True)
+    for e in envs:
+        e.close()
+
+
+if __name__ == "__main__":
+    main()

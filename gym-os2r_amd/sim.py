@@ -516,9 +516,9 @@ class HipSim:
                 ja.permute(2, 0, 1) if want_A else None, jb.permute(2, 0, 1) if want_B else None)
 
     # -- LQR gains --------------------------------------------------------------------------
-    def _lqr_cost(self, Q, R):
+    def _lqr_cost(self, Q, R, what="lqr_gains"):
         """Q [2nq, 2nq] and R [2, 2] of lqr_gains() -> two ctypes double arrays (row-major), checked: host values, finite and
-        exactly symmetric (include/os2r.h: os2r_lqr_gains)."""
+        exactly symmetric (include/os2r.h: os2r_lqr_gains).  `what`: the method the errors name."""
         n = 2 * self.nq
         out = []
         for name, m, k in (("Q", Q, n), ("R", R, 2)):
@@ -529,13 +529,13 @@ class HipSim:
                     import numpy as np
                     t = torch.from_numpy(np.array(m, dtype=np.float64))
             except (TypeError, ValueError, RuntimeError):
-                raise ValueError(f"lqr_gains: {name} must be a [{k}, {k}] array of numbers, got {type(m)}") from None
+                raise ValueError(f"{what}: {name} must be a [{k}, {k}] array of numbers, got {type(m)}") from None
             if tuple(t.shape) != (k, k):
-                raise ValueError(f"lqr_gains: {name} must have shape ({k}, {k}), got {tuple(t.shape)}")
+                raise ValueError(f"{what}: {name} must have shape ({k}, {k}), got {tuple(t.shape)}")
             if not bool(torch.isfinite(t).all()):
-                raise ValueError(f"lqr_gains: {name} must be finite")
+                raise ValueError(f"{what}: {name} must be finite")
             if not bool((t == t.T).all()):
-                raise ValueError(f"lqr_gains: {name} must be exactly symmetric")
+                raise ValueError(f"{what}: {name} must be exactly symmetric")
             out.append((C.c_double * (k * k))(*t.reshape(-1).tolist()))
         return out
 
@@ -628,6 +628,148 @@ class HipSim:
                             obs=ob, weights_out=wts)
         return (gains.permute(0, 3, 1, 2) if want_gains else None, pout.permute(2, 0, 1) if want_P else None, flags,
                 wts.permute(3, 0, 1, 2) if want_weights else None)
+
+    # -- iLQR backward pass -----------------------------------------------------------------
+    def _ilqr_scalars(self, mu, alphas, want_weights):
+        """mu and alphas of ilqr_backward() -> (float, ctypes double array or None), checked."""
+        import math
+        try:
+            mu = float(mu)
+        except (TypeError, ValueError):
+            raise ValueError(f"ilqr_backward: mu must be a number, got {type(mu)}") from None
+        if not math.isfinite(mu) or mu < 0.0:
+            raise ValueError(f"ilqr_backward: mu must be finite and >= 0, got {mu}")
+        if not want_weights:
+            return mu, None
+        try:
+            al = [float(v) for v in (alphas.tolist() if hasattr(alphas, "tolist") else alphas)]
+        except (TypeError, ValueError):
+            raise ValueError(f"ilqr_backward: alphas must be a sequence of numbers, got {type(alphas)}") from None
+        if not 1 <= len(al) <= 16:
+            raise ValueError(f"ilqr_backward: between 1 and 16 alphas, got {len(al)}")
+        if not all(math.isfinite(v) for v in al):
+            raise ValueError(f"ilqr_backward: every alpha must be finite, got {al}")
+        return mu, (C.c_double * len(al))(*al)
+
+    def ilqr_backward_into(self, A, B, Q, R, *, knots: int = 1, lx=None, lu=None, mu: float = 0.0, P_final=None, p_final=None,
+                           gains_out=None, ff_out=None, P_out=None, p_out=None, flags_out=None, dv_out=None, actions=None, obs=None,
+                           alphas=None, weights_out=None):
+        """Allocation-free variant of ilqr_backward() on tensors in the kernel's layout (include/os2r_control.h:
+        os2rc_ilqr_backward), the trajectory index fastest: with K = knots, L = K M and n = 2nq, A [n, n, L], B [n, 2, L],
+        lx [n, L], lu [2, L], P_final [n, n, M], p_final [n, M] (each of the four None for its default), gains_out [K, 2, n, M],
+        ff_out [K, 2, M], P_out [n, n, M] (may be P_final), p_out [n, M] (may be p_final), flags_out [K, M] uint8,
+        dv_out [K, 2, M], weights_out [K, 2, D+1, len(alphas) M] with actions [L, 2], obs [L, D] and alphas; each output may be
+        None, not all of them but flags_out.  Shapes, dtypes, device and contiguity are checked before the library is called (it
+        takes addresses)."""
+        n = 2 * self.nq
+        K = int(knots)
+        if K < 1:
+            raise ValueError(f"ilqr_backward: knots must be >= 1, got {K}")
+        q, r = self._lqr_cost(Q, R, "ilqr_backward")
+        if not isinstance(A, torch.Tensor) or A.dim() != 3:
+            raise ValueError(f"ilqr_backward: A must be a tensor of shape ({n}, {n}, knots * M)")
+        L = int(A.shape[2])
+        if L < K or L % K:
+            raise ValueError(f"ilqr_backward: the {L} lanes of A are no multiple of knots = {K}")
+        M = L // K
+        if all(t is None for t in (gains_out, ff_out, P_out, p_out, dv_out, weights_out)):
+            raise ValueError("ilqr_backward: nothing asked for (gains, ff, P, p, dv and weights are all off)")
+        if weights_out is not None and (actions is None or obs is None or alphas is None):
+            raise ValueError("ilqr_backward: weights need actions, obs (the point each knot was linearised about) and alphas")
+        mu, al = self._ilqr_scalars(mu, alphas, weights_out is not None)
+        if B is None:
+            raise ValueError("ilqr_backward: B is required")
+        for t, shape, name in ((A, (n, n, L), "A"), (B, (n, 2, L), "B"), (lx, (n, L), "lx"), (lu, (2, L), "lu"),
+                               (P_final, (n, n, M), "P_final"), (p_final, (n, M), "p_final"), (gains_out, (K, 2, n, M), "gains_out"),
+                               (ff_out, (K, 2, M), "ff_out"), (P_out, (n, n, M), "P_out"), (p_out, (n, M), "p_out"),
+                               (dv_out, (K, 2, M), "dv_out")):
+            self._out(t, shape, self.dtype, f"ilqr_backward: {name}")
+        self._out(flags_out, (K, M), torch.uint8, "ilqr_backward: flags_out")
+        nal = 0
+        if weights_out is not None:
+            nal = len(al)
+            self._out(weights_out, (K, 2, self.D + 1, nal * M), self.dtype, "ilqr_backward: weights_out")
+            self._out(actions, (L, 2), self.dtype, "ilqr_backward: actions")
+            self._out(obs, (L, self.D), self.dtype, "ilqr_backward: obs")
+        else:
+            actions = obs = None
+        from . import control
+        lib = control.load()
+        lay = self.__dict__.get("_control_layout")
+        if lay is None:       # filled once from the handle's config
+            lay = self._control_layout = control.layout(abi.F64 if self.dtype == torch.float64 else abi.F32, self.nq, self.cfg.device,
+                                                        control.slot_columns(self.cfg.task, self.nq))
+        rc = lib.os2rc_ilqr_backward(C.byref(lay), K, M, _ptr(A), _ptr(B), _ptr(lx), _ptr(lu), q, r, mu, _ptr(P_final), _ptr(p_final),
+                                     _ptr(gains_out), _ptr(ff_out), _ptr(P_out), _ptr(p_out), _ptr(flags_out), _ptr(dv_out), _ptr(actions),
+                                     _ptr(obs), al, nal, _ptr(weights_out), self._stream())
+        if rc != abi.OK:
+            raise Os2rError(f"os2rc_ilqr_backward failed ({rc}): {lib.os2rc_last_error().decode()}")
+
+    def ilqr_backward(self, A, B, Q, R, *, knots, lx=None, lu=None, mu=0.0, P_final=None, p_final=None, actions=None, obs=None,
+                      alphas=None, want_gains=True, want_ff=True, want_P=False, want_p=False, want_flags=True, want_dv=True,
+                      want_weights=False):
+        """The backward pass of iLQR for M = L / knots independent trajectories in one launch (include/os2r_control.h:
+        os2rc_ilqr_backward; the arithmetic and its order are spelled out there): lqr_gains(sweeps=1) with its affine terms.
+        A [L, 2nq, 2nq] and B [L, 2nq, 2] as linearize() returns them (taken without a copy), lane k * M + m knot k of trajectory
+        m; lx [L, 2nq] and lu [L, 2] the cost gradients at the knots (None: zeros); Q, R the cost Hessians as in lqr_gains;
+        mu >= 0 the control-space regularisation; P_final [M, 2nq, 2nq] (None: Q) and p_final [M, 2nq] (None: zeros) the value
+        function behind the last knot.
+        -> (gains [K, M, 2, 2nq], ff [K, M, 2], P [M, 2nq, 2nq], p [M, 2nq], flags [K, M] uint8, dv [K, M, 2],
+        weights [len(alphas) M, K, 2, D+1]), None where not wanted; all are permuted views of the kernel's layouts.  The control
+        law of knot k is a = a_k + alpha ff_k - gains_k (x - x_k); flags is 1 where a knot's regularised 2 x 2 system was refused
+        (gains and ff are 0 there); alpha dv[..., 0].sum(0) + alpha^2 dv[..., 1].sum(0) is the model's cost change under step size
+        alpha.  weights (needs actions [L, 2], obs [L, D] and alphas) is the per-environment table rollout_schedule takes for a
+        handle of len(alphas) M environments, environment i M + m being trajectory m under alphas[i]."""
+        n = 2 * self.nq
+        K = int(knots)
+        if K < 1:
+            raise ValueError(f"ilqr_backward: knots must be >= 1, got {K}")
+        if not (want_gains or want_ff or want_P or want_p or want_dv or want_weights):
+            raise ValueError("ilqr_backward: nothing asked for (gains, ff, P, p, dv and weights are all off)")
+        if want_weights and (actions is None or obs is None or alphas is None):
+            raise ValueError("ilqr_backward: weights need actions, obs (the point each knot was linearised about) and alphas")
+        self._lqr_cost(Q, R, "ilqr_backward")
+        _, al = self._ilqr_scalars(mu, alphas, want_weights)
+        for name, t, w in (("A", A, n), ("B", B, 2)):
+            if not isinstance(t, torch.Tensor) or t.dim() != 3 or tuple(t.shape[1:]) != (n, w):
+                raise ValueError(f"ilqr_backward: {name} must be a tensor of shape (knots * M, {n}, {w}), got "
+                                 f"{tuple(getattr(t, 'shape', ())) or type(t)}")
+            if t.dtype != self.dtype or t.device != self.device:
+                raise ValueError(f"ilqr_backward: {name} must be {self.dtype} on {self.device}, got {t.dtype} on {t.device}")
+        L = int(A.shape[0])
+        if int(B.shape[0]) != L:
+            raise ValueError(f"ilqr_backward: A has {L} lanes, B {int(B.shape[0])}")
+        if L < K or L % K:
+            raise ValueError(f"ilqr_backward: the {L} lanes of A are no multiple of knots = {K}")
+        M = L // K
+        a, b = A.permute(1, 2, 0).contiguous(), B.permute(1, 2, 0).contiguous()     # no copy for what linearize() returned
+
+        def given(t, shape, name, perm):
+            if t is None:
+                return None
+            try:
+                return self._in(t, shape).permute(*perm).contiguous()
+            except ValueError as e:
+                raise ValueError(f"ilqr_backward: {name}: {e}") from None
+        gx, gu = given(lx, (L, n), "lx", (1, 0)), given(lu, (L, 2), "lu", (1, 0))
+        pf, vf = given(P_final, (M, n, n), "P_final", (1, 2, 0)), given(p_final, (M, n), "p_final", (1, 0))
+        act = ob = None
+        nal = 0
+        if want_weights:
+            nal = len(al)
+            act, ob = given(actions, (L, 2), "actions", (0, 1)), given(obs, (L, self.D), "obs", (0, 1))
+        gains = self._new(K, 2, n, M) if want_gains else None
+        ff = self._new(K, 2, M) if want_ff else None
+        pout = self._new(n, n, M) if want_P else None
+        vout = self._new(n, M) if want_p else None
+        flags = self._new(K, M, dtype=torch.uint8) if want_flags else None
+        dv = self._new(K, 2, M) if want_dv else None
+        wts = self._new(K, 2, self.D + 1, nal * M) if want_weights else None
+        self.ilqr_backward_into(a, b, Q, R, knots=K, lx=gx, lu=gu, mu=mu, P_final=pf, p_final=vf, gains_out=gains, ff_out=ff, P_out=pout,
+                                p_out=vout, flags_out=flags, dv_out=dv, actions=act, obs=ob, alphas=alphas, weights_out=wts)
+        return (gains.permute(0, 3, 1, 2) if want_gains else None, ff.permute(0, 2, 1) if want_ff else None,
+                pout.permute(2, 0, 1) if want_P else None, vout.permute(1, 0) if want_p else None, flags,
+                dv.permute(0, 2, 1) if want_dv else None, wts.permute(3, 0, 1, 2) if want_weights else None)
 
     def action_violations_into(self, dst: torch.Tensor, clear: bool = True):
         """Copy the running count of out-of-range caller actions into ``dst`` (one int32/uint32 element,
