@@ -3,12 +3,13 @@
 by side towards a target posture, the backward pass in one os2rc_ilqr_backward launch.
 
   python examples/ilqr_balancing.py [--envs 64] [--steps 40] [--iters 10] [--settle 300] [--perturb 0.05] [--mu 0.0] [--eps 1e-4]
+                                    [--knots recorded|loop]
 
 The cost of a trajectory is sum_k 1/2 (x_k - x*)'Q(x_k - x*) + 1/2 a_k'R a_k plus 1/2 (x_K - x*)'Q(x_K - x*), read off the raw
 observation slots (state components the task does not observe carry no weight); x* is the posture the PD of lqr_balancing.py
-settles in, the starts are that posture perturbed, the first nominal is zero torque.  Each iteration:
+settles in, the starts are that posture perturbed, the first nominal is zero torque.  Each iteration (--knots loop):
   1. the nominal is replayed from the start and knot k of trajectory m forked into lane k M + m of a K M-lane handle
-     (copy_envs_from, one launch per knot);
+     (copy_envs_from, one launch per knot: 2 K launches);
   2. one os2r_linearize launch returns A_k, B_k of every knot;
   3. lx = Q (x_k - x*), lu = R a_k and p_final = Q (x_K - x*) are formed in torch;
   4. one ilqr_backward launch returns the refusal flags, the two terms of the expected cost change and ONE table of weights
@@ -18,6 +19,13 @@ settles in, the starts are that posture perturbed, the first nominal is zero tor
   6. their costs are read off the returned observations and actions;
   7. the best step size that lowers the summed cost is accepted (its applied actions are the new nominal); if none does, mu is
      raised and the iteration repeated.
+With --knots recorded (the default) step 1 is gone: the rollout of step 5 records the knots of every candidate into a handle of
+K 4 M lanes and their observations (rollout_schedule(..., knots=..., want_knot_obs=True): the same launch), and accepting a step
+size moves its knots into the K M-lane handle with one copy_envs_from; the observations at the knots and the actions are views
+of what that launch returned.  An iteration is five launches: linearize, ilqr_backward, copy_envs_from (knot 0 -> candidates),
+rollout_schedule, copy_envs_from (the accepted knots).  The first nominal comes from one recorded rollout whose table has zero
+gains and the actions as bias.  Both modes visit the same states bit for bit and print the same costs (as long as no episode ends
+inside a trajectory: an auto-reset draws from the lane's own random stream, and a candidate's lane is not the nominal's).
 Printed per iteration: the cost (mean over the trajectories), the step size, mu, the refused knots, and the predicted against
 the actual change.  The script prints what happened; it claims no control quality: a quotient across a change of contact mode
 is a secant, the default eps is not tuned, and the actions saturate, which the model knows nothing about.
@@ -48,13 +56,19 @@ def main():
     ap.add_argument("--kp", type=float, default=8.0)
     ap.add_argument("--kd", type=float, default=0.15)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--knots", choices=("recorded", "loop"), default="recorded",
+                    help="recorded: the candidates' rollout records the knots (five launches per iteration); loop: the nominal is "
+                         "replayed and forked knot by knot")
     args = ap.parse_args()
     M, K, nal = args.envs, args.steps, len(ALPHAS)
-    # one task, three handles: the nominal (M trajectories), the knots (K M lanes, knot-major), the candidates (4 M environments)
-    envs = [g.make("Monopod-nonorm-balance-v1", num_envs=n, seed=args.seed) for n in (M, K * M, nal * M)]
+    recorded = args.knots == "recorded"
+    # one task, three handles: the nominal (M trajectories), the knots (K M lanes, knot-major), the candidates (4 M environments);
+    # recorded: a fourth for the knots of every candidate (K 4 M lanes, knot-major)
+    envs = [g.make("Monopod-nonorm-balance-v1", num_envs=n, seed=args.seed) for n in (M, K * M, nal * M) + ((K * nal * M,) if recorded else ())]
     for e in envs:
         e.reset()
-    nom, knots, cand = (e.sim for e in envs)
+    nom, knots, cand = (e.sim for e in envs[:3])
+    cand_knots = envs[3].sim if recorded else None
     dev, dt, nq, D = nom.device, nom.dtype, nom.nq, nom.D
     n = 2 * nq
     cols = slot_columns(nom.cfg.task, nq)
@@ -94,17 +108,27 @@ def main():
     first = torch.arange(M, dtype=torch.int32, device=dev).repeat(nal)                # knot 0 of trajectory m, once per step size
     U = torch.zeros(K, M, 2, dtype=dt, device=dev)
     mu, it, tries, shown_cost = args.mu, 0, 0, None
+    if recorded:
+        # the first nominal, recorded: zero gains, the actions as bias (b + 0 o = b: the open-loop actions, bit for bit)
+        table0 = torch.zeros(M, K, 2, D + 1, dtype=dt, device=dev)
+        table0[:, :, :, D] = U.permute(1, 0, 2)
+        nom.restore(start)
+        _, _, (o_n, _, d_n, _, _), _, kobs = nom.rollout_schedule(K, table0, want_outputs=True, knots=knots, want_knot_obs=True)
+        ended, end_obs, obs_k = int((d_n != 0).sum()), o_n[K - 1], kobs.view(K * M, D)
+        lane = torch.arange(K * M, dtype=torch.int32, device=dev)
+        best_lanes = [(lane // M) * (nal * M) + b * M + lane % M for b in range(nal)]    # knot k of trajectory m under step size b
     while it < args.iters and tries < 4 * args.iters:
         tries += 1
-        # 1. replay the nominal, fork the knots
-        nom.restore(start)
-        ended = 0
-        for k in range(K):
-            knots.copy_envs_from(nom, fork[k])
-            _, _, done, _ = nom.step(U[k], want_terminal=False)
-            ended += int((done != 0).sum())
-        end_obs = nom.copy_envs_from(nom, want_obs=True)
-        obs_k = knots.copy_envs_from(knots, want_obs=True)                            # [K M, D]: the observation at each knot
+        if not recorded:
+            # 1. replay the nominal, fork the knots
+            nom.restore(start)
+            ended = 0
+            for k in range(K):
+                knots.copy_envs_from(nom, fork[k])
+                _, _, done, _ = nom.step(U[k], want_terminal=False)
+                ended += int((done != 0).sum())
+            end_obs = nom.copy_envs_from(nom, want_obs=True)
+            obs_k = knots.copy_envs_from(knots, want_obs=True)                        # [K M, D]: the observation at each knot
         J = cost(torch.cat([obs_k.view(K, M, D), end_obs[None]]), U)
         if shown_cost is None:
             shown_cost = float(J.mean())
@@ -124,7 +148,11 @@ def main():
         refused = int(flags.sum())
         # 5. all candidates of all trajectories in one launch, from knot 0
         cand.copy_envs_from(knots, first)
-        _, _, (o_c, _, d_c, _, _), (a_c, _) = cand.rollout_schedule(K, table, want_outputs=True, want_actions=True)
+        if recorded:
+            _, _, (o_c, _, d_c, _, _), (a_c, _), kobs_c = cand.rollout_schedule(K, table, want_outputs=True, want_actions=True,
+                                                                              knots=cand_knots, want_knot_obs=True)
+        else:
+            _, _, (o_c, _, d_c, _, _), (a_c, _) = cand.rollout_schedule(K, table, want_outputs=True, want_actions=True)
         # 6. their costs
         J_c = cost(torch.cat([obs_k[:M].repeat(nal, 1)[None], o_c]), a_c).view(nal, M)
         # 7. the best step size that lowers the summed cost, or more regularisation
@@ -140,6 +168,11 @@ def main():
                   f"{predicted:+.4e} actual {actual:+.4e}; {int((d_c.view(K, nal, M)[:, best] != 0).any(0).sum())} of {M} episodes ended",
                   flush=True)
             U = a_c.view(K, nal, M, 2)[:, best].contiguous()
+            if recorded:
+                # the accepted candidate is the new nominal: its knots in one launch, its observations as they were recorded
+                knots.copy_envs_from(cand_knots, best_lanes[best])
+                obs_k = kobs_c.view(K, nal, M, D)[:, best].reshape(K * M, D)
+                end_obs = o_c[K - 1].view(nal, M, D)[best]
             mu = 0.5 * mu if mu > 1e-3 else 0.0
         else:
             print(f"        no step size lowers the cost at mu {mu:.3e} (best alpha {ALPHAS[best]}: {float(total[best] - J.sum()) / M:+.4e}, "

@@ -61,8 +61,40 @@ ENTRY_POINTS = {
 SYMBOLS = list(ENTRY_POINTS)
 
 
+# The companion library libos2r_record.so (include/os2r_record.h): built from the same objects, working on the same handles.  A
+# table of its own: libos2r.so's symbol table is ENTRY_POINTS and nothing else.
+RECORD_LIB_PATH = os.environ.get("OS2R_RECORD_LIBRARY") or os.path.join(_HERE, "libos2r_record.so")
+RECORD_ENTRY_POINTS = {
+    "os2rr_rollout_policy_recorded": (_vp, _vp, _i32, _i32, _vp, C.c_int, _vp, _i32, _i32, _i32, _vp, C.c_uint32) + (_vp,) * 10,
+    "os2rr_last_error": (),
+    "os2rr_abi_version": (),
+}
+RECORD_ABI_VERSION = 1
+_record = None
+
+
 class Os2rLibraryMissing(ImportError):
     pass
+
+
+def load_record():
+    """libos2r_record.so through ctypes (after libos2r.so, and so after torch: one HIP runtime per process)."""
+    global _record
+    if _record is not None:
+        return _record
+    load()
+    if not os.path.exists(RECORD_LIB_PATH):
+        raise Os2rLibraryMissing(f"{RECORD_LIB_PATH} not found: it is built with libos2r.so (make -C gym-os2r_amd/csrc); without it "
+                                 "no rollout can record its knots")
+    lib = C.CDLL(RECORD_LIB_PATH)
+    for name, argtypes in RECORD_ENTRY_POINTS.items():
+        fn = getattr(lib, name)
+        fn.argtypes = list(argtypes)
+        fn.restype = C.c_char_p if name == "os2rr_last_error" else C.c_int
+    if lib.os2rr_abi_version() != RECORD_ABI_VERSION:
+        raise ImportError("libos2r_record.so ABI version does not match gym_os2r_amd._lib")
+    _record = lib
+    return lib
 
 
 def load():
@@ -110,14 +142,14 @@ def _converter(argtype):
     return _a if issubclass(argtype, (C.c_void_p, C._Pointer)) else int
 
 
-def _forward(name, argtypes):
+def _forward(name, argtypes, prefix="os2r_"):
     """`def os2r_x(self, a0, a1, ...): return self.m.x(_a(a0), int(a1), ...)`: the method of one entry point as it would be
     written by hand, the converter of every argument fixed here.  (Made from source, not as a closure over a tuple of
     converters: a loop over the arguments in every call cost a third more on os2r_step, and this one checks the arity.)"""
     args = [f"a{i}" for i in range(len(argtypes))]
     converted = ", ".join(f"{_converter(t).__name__}({a})" for t, a in zip(argtypes, args))
     scope = {"_a": _a, "_s": _s, "__name__": __name__}
-    exec(f"def {name}(self, {', '.join(args)}): return self.m.{name[len('os2r_'):]}({converted})", scope)
+    exec(f"def {name}(self, {', '.join(args)}): return self.m.{name[len(prefix):]}({converted})", scope)
     scope[name].__qualname__ = f"_PybindLib.{name}"
     return scope[name]
 
@@ -166,7 +198,13 @@ class _PybindLib:
     def os2r_last_error(self, h):
         return self.m.last_error(_a(h)).encode()
 
+    # libos2r_record.so: the module links it too
+    def os2rr_last_error(self):
+        return self.m.record_last_error().encode()
+
 
 for _name, _argtypes in ENTRY_POINTS.items():
     if _name not in vars(_PybindLib):
         setattr(_PybindLib, _name, _forward(_name, _argtypes))
+setattr(_PybindLib, "os2rr_rollout_policy_recorded",
+        _forward("os2rr_rollout_policy_recorded", RECORD_ENTRY_POINTS["os2rr_rollout_policy_recorded"], prefix="os2rr_"))

@@ -18,6 +18,7 @@
 
 #include "os2r_kernels.hpp"
 #include "os2r_lqr.hpp"
+#include "../../include/os2r_record.h"
 
 using namespace os2r;
 
@@ -44,6 +45,9 @@ struct JitEntry {
   int fused_dim = -1;
   // os2r_jit_lin_c*_d* (_s): [contact][per-env parameters][default sweep counts compiled in], as fn
   hipFunction_t fn_lin[2][2][2] = {};
+  // os2r_jit_policy_rec_c1_d*: the policy kernels that record the knots (os2rr_rollout_policy_recorded); kept only from an object
+  // that announces the sink with the data symbol os2r_jit_policy_knots
+  hipFunction_t fn_policy_rec[2] = {};
 };
 enum JitKind { kJitStep, kJitRollout, kJitPolicy, kJitLin };
 
@@ -480,67 +484,6 @@ int upload_model(Os2rSim* s) {
   return OS2R_OK;
 }
 
-// K env-steps with the linear policy in the loop: one launch of the fused kernel where os2r_rollout has a fused variant;
-// otherwise per env-step the policy kernel (state -> observation -> actions), the step launch with those actions and the
-// accumulation of the step's reward and done flag (same results)
-template <typename T>
-int do_rollout_policy(Os2rSim* s, int K, const void* w, int flags, void* ret, int32_t* len, void* obs, void* reward, uint8_t* done,
-                      void* term, uint16_t* reason, hipStream_t st, const void* sigma = nullptr, uint32_t salt = 0u,
-                      void* act_out = nullptr, void* eps_out = nullptr, int period = 0, int first_slot = 0) {
-  const size_t N = (size_t)s->cfg.num_envs, D = (size_t)s->D;
-  PolicyArgs<T> p;
-  std::memset(&p, 0, sizeof(p));
-  p.w = (const T*)w; p.flags = flags; p.ret = (T*)ret; p.len = len;
-  // exploration noise (os2r_rollout_policy_noisy): a null sigma is the deterministic policy
-  p.sigma = (const T*)sigma; p.salt = salt; p.act_out = (T*)act_out; p.eps_out = (T*)eps_out;
-  // time schedule (os2r_rollout_policy_scheduled): period 0 is the one set of the two entry points above
-  p.period = period; p.first_slot = first_slot;
-  const hipFunction_t jit_fn = jit_fused_fn<T>(s, s->jit_policy ? s->jit_policy->fn_policy : nullptr);
-  if ((!s->jit || jit_fn) && !s->counters) {
-    p.s = make_args<T>(s);
-    p.s.obs = (T*)obs; p.s.reward = (T*)reward; p.s.done = done; p.s.term_obs = (T*)term; p.s.reason = reason;
-    p.s.done_mask = nullptr;   // (neither of the per-step buffers set on the handle is written)
-    p.s.rollout_steps = K;
-    if (jit_fn) HIP_TRY(s, jit_launch(jit_fn, p, p.s.N, 1, st));
-    if (jit_fn || Launcher<T>::policy_rollout(s->model_id, s->cfg.contact != 0, s->dr, p, st) == 0) {
-      HIP_TRY(s, hipGetLastError());
-      s->step_count += (unsigned long long)K;
-      return OS2R_OK;
-    }
-  }
-  int rc = OS2R_OK;
-  if (!s->pol_act) {
-    if ((rc = dev_alloc(s, &s->pol_act, 2 * N * s->esz))) return rc;
-    if ((rc = dev_alloc(s, (void**)&s->pol_open, N))) return rc;
-  }
-  p.act = (T*)s->pol_act; p.open = s->pol_open;
-  uint16_t* const reason_keep = s->reason;
-  uint8_t* const mask_keep = s->done_mask;
-  s->done_mask = nullptr;
-  for (int k = 0; k < K && rc == OS2R_OK; ++k) {
-    p.s = make_args<T>(s);   // (with it the step counter of env-step k, which keys the noise)
-    p.act_out = act_out ? (T*)act_out + (size_t)k * N * 2 : nullptr;
-    p.eps_out = eps_out ? (T*)eps_out + (size_t)k * N * 2 : nullptr;
-    if (period > 0 && !(flags & OS2R_POLICY_CLOCK_EPISODE)) {
-      // the window clock of env-step k, reduced to its slot here (the sum may not fit 32 bits); the kernel's rule leaves a slot as it is
-      const long long t = (long long)first_slot + k;
-      p.first_slot = (int)((flags & OS2R_POLICY_SCHEDULE_WRAP) ? t % period : (t < period - 1 ? t : period - 1));
-    }
-    if (Launcher<T>::policy(s->nq, p, st) != 0) { s->err = "no policy kernel for this chain length"; rc = OS2R_ERR_INVALID; break; }
-    // the sums need the step's reward and done flag: the handle's scratch outputs stand in for the ones not asked for
-    T* const rew_k = reward ? (T*)reward + (size_t)k * N : (T*)s->b_rew;
-    uint8_t* const done_k = done ? done + (size_t)k * N : s->b_done;
-    s->reason = reason ? reason + (size_t)k * N : nullptr;
-    rc = do_step<T>(s, s->pol_act, obs ? (T*)obs + (size_t)k * N * D : nullptr, rew_k, done_k, term ? (T*)term + (size_t)k * N * D : nullptr, st);
-    if (rc == OS2R_OK && (ret || len))
-      Launcher<T>::accumulate((T*)ret, len, s->pol_open, rew_k, done_k, (long long)N, k, (flags & OS2R_POLICY_FIRST_EPISODE) != 0, st);
-  }
-  s->reason = reason_keep;
-  s->done_mask = mask_keep;
-  if (rc == OS2R_OK) HIP_TRY(s, hipGetLastError());
-  return rc;
-}
-
 // The rows `what` selects, as the copy kernel takes them: row r of an array of the source next to row r of the same array of the
 // destination.  `stage` (the in-place case) stands in for the destination (to_stage) or for the source: it holds every row
 // once, [row][num_envs of the handle], the 32-bit rows and the pose bytes behind the rows of the handle's dtype.
@@ -576,6 +519,111 @@ CopyArgs<T> copy_rows(Os2rSim* d, Os2rSim* s, int what, void* stage, bool to_sta
     rows(s->mu, d->mu, nq); rows(s->gravity, d->gravity, 1);
   }
   return a;
+}
+
+// os2rr_rollout_policy_recorded: where the knots of a policy rollout go
+struct KnotSink {
+  Os2rSim* knots;   // nullable
+  int first_knot, what;
+  void* obs;        // nullable, [K][N][D]
+};
+
+// do_copy's rule for the destination of a parameter copy: from a source with per-environment parameters (or another gravity) it
+// reads its parameter arrays per lane from now on
+inline void knots_read_params(Os2rSim* kn, const Os2rSim* s, const KnotSink* sink) {
+  if (kn && (sink->what & OS2R_COPY_PARAMS) && (s->dr || s->cfg.model.gravity_z != kn->cfg.model.gravity_z)) kn->dr = true;
+}
+
+// K env-steps with the linear policy in the loop: one launch of the fused kernel where os2r_rollout has a fused variant;
+// otherwise per env-step the policy kernel (state -> observation -> actions), the step launch with those actions and the
+// accumulation of the step's reward and done flag (same results)
+// (os2rr_rollout_policy_recorded: with `sink` the environments of the top of env-step k go to lanes (first_knot + k) N .. of
+// sink->knots and their observations to sink->obs -- by the fused kernel itself, or in the launch loop by one copy launch per
+// env-step and the policy kernel)
+template <typename T>
+int do_rollout_policy(Os2rSim* s, int K, const void* w, int flags, void* ret, int32_t* len, void* obs, void* reward, uint8_t* done,
+                      void* term, uint16_t* reason, hipStream_t st, const void* sigma = nullptr, uint32_t salt = 0u,
+                      void* act_out = nullptr, void* eps_out = nullptr, int period = 0, int first_slot = 0,
+                      const KnotSink* sink = nullptr) {
+  const size_t N = (size_t)s->cfg.num_envs, D = (size_t)s->D;
+  PolicyArgs<T> p;
+  std::memset(&p, 0, sizeof(p));
+  p.w = (const T*)w; p.flags = flags; p.ret = (T*)ret; p.len = len;
+  // exploration noise (os2r_rollout_policy_noisy): a null sigma is the deterministic policy
+  p.sigma = (const T*)sigma; p.salt = salt; p.act_out = (T*)act_out; p.eps_out = (T*)eps_out;
+  // time schedule (os2r_rollout_policy_scheduled): period 0 is the one set of the two entry points above
+  p.period = period; p.first_slot = first_slot;
+  // (a recorded call takes the recording kernels of the policy object; one that has none -- it would take the appended arguments
+  // and record nothing -- leaves the call to the launch loop)
+  const hipFunction_t jit_fn = jit_fused_fn<T>(s, !s->jit_policy ? nullptr : sink ? s->jit_policy->fn_policy_rec : s->jit_policy->fn_policy);
+  Os2rSim* const kn = sink ? sink->knots : nullptr;
+  if ((!s->jit || jit_fn) && !s->counters) {
+    if (sink) {
+      p.knot_obs = (T*)sink->obs;
+      if (kn) {
+        p.knot_what = sink->what; p.knot_stride = kn->cfg.num_envs; p.knot_lane = (long long)sink->first_knot * (long long)N;
+        p.kq = (T*)kn->q; p.kqd = (T*)kn->qd; p.khist = (T*)kn->hist; p.ksolver_l = (T*)kn->solver_l;
+        p.ksolver_flags = kn->solver_flags; p.ksteps = kn->steps; p.kepisode = kn->episode; p.kpose = kn->pose;
+        p.kmass_scale = (T*)kn->mass_scale; p.kdamping = (T*)kn->damping; p.kfriction = (T*)kn->friction; p.kmu = (T*)kn->mu;
+        p.kgravity = (T*)kn->gravity;
+      }
+    }
+    p.s = make_args<T>(s);
+    p.s.obs = (T*)obs; p.s.reward = (T*)reward; p.s.done = done; p.s.term_obs = (T*)term; p.s.reason = reason;
+    p.s.done_mask = nullptr;   // (neither of the per-step buffers set on the handle is written)
+    p.s.rollout_steps = K;
+    if (jit_fn) HIP_TRY(s, jit_launch(jit_fn, p, p.s.N, 1, st));
+    if (jit_fn || Launcher<T>::policy_rollout(s->model_id, s->cfg.contact != 0, s->dr, p, st) == 0) {
+      HIP_TRY(s, hipGetLastError());
+      s->step_count += (unsigned long long)K;
+      knots_read_params(kn, s, sink);
+      return OS2R_OK;
+    }
+    p.knot_what = 0;   // (no fused variant after all: the launch loop copies, and its policy kernel takes nothing of the sink but knot_obs)
+  }
+  int rc = OS2R_OK;
+  if (!s->pol_act) {
+    if ((rc = dev_alloc(s, &s->pol_act, 2 * N * s->esz))) return rc;
+    if ((rc = dev_alloc(s, (void**)&s->pol_open, N))) return rc;
+  }
+  p.act = (T*)s->pol_act; p.open = s->pol_open;
+  uint16_t* const reason_keep = s->reason;
+  uint8_t* const mask_keep = s->done_mask;
+  s->done_mask = nullptr;
+  for (int k = 0; k < K && rc == OS2R_OK; ++k) {
+    p.s = make_args<T>(s);   // (with it the step counter of env-step k, which keys the noise)
+    p.act_out = act_out ? (T*)act_out + (size_t)k * N * 2 : nullptr;
+    p.eps_out = eps_out ? (T*)eps_out + (size_t)k * N * 2 : nullptr;
+    if (period > 0 && !(flags & OS2R_POLICY_CLOCK_EPISODE)) {
+      // the window clock of env-step k, reduced to its slot here (the sum may not fit 32 bits); the kernel's rule leaves a slot as it is
+      const long long t = (long long)first_slot + k;
+      p.first_slot = (int)((flags & OS2R_POLICY_SCHEDULE_WRAP) ? t % period : (t < period - 1 ? t : period - 1));
+    }
+    if (kn) {
+      // knot first_knot + k: the copy kernel with the destination's rows moved to the knot's first lane, N lanes, the identity map
+      CopyArgs<T> c = copy_rows<T>(kn, s, sink->what, nullptr, false);
+      const size_t lane0 = ((size_t)sink->first_knot + (size_t)k) * N;
+      for (int r = 0; r < c.nrows; ++r) c.dst[r] += lane0;
+      for (int r = 0; r < c.nwords; ++r) c.dst32[r] += lane0;
+      if (c.dst8) c.dst8 += lane0;
+      c.Nd = c.Ns = (long long)N; c.index = nullptr;
+      Launcher<T>::copy_envs(c, st);
+    }
+    p.knot_obs = sink && sink->obs ? (T*)sink->obs + (size_t)k * N * D : nullptr;
+    if (Launcher<T>::policy(s->nq, p, st) != 0) { s->err = "no policy kernel for this chain length"; rc = OS2R_ERR_INVALID; break; }
+    // the sums need the step's reward and done flag: the handle's scratch outputs stand in for the ones not asked for
+    T* const rew_k = reward ? (T*)reward + (size_t)k * N : (T*)s->b_rew;
+    uint8_t* const done_k = done ? done + (size_t)k * N : s->b_done;
+    s->reason = reason ? reason + (size_t)k * N : nullptr;
+    rc = do_step<T>(s, s->pol_act, obs ? (T*)obs + (size_t)k * N * D : nullptr, rew_k, done_k, term ? (T*)term + (size_t)k * N * D : nullptr, st);
+    if (rc == OS2R_OK && (ret || len))
+      Launcher<T>::accumulate((T*)ret, len, s->pol_open, rew_k, done_k, (long long)N, k, (flags & OS2R_POLICY_FIRST_EPISODE) != 0, st);
+  }
+  s->reason = reason_keep;
+  s->done_mask = mask_keep;
+  if (rc == OS2R_OK) HIP_TRY(s, hipGetLastError());
+  if (rc == OS2R_OK) knots_read_params(kn, s, sink);
+  return rc;
 }
 
 template <typename T>
@@ -881,6 +929,39 @@ int os2r_rollout_policy_scheduled(Os2rSim* sim, int nsteps, const void* weights_
   });
 }
 
+int os2rr_rollout_policy_recorded(Os2rSim* sim, Os2rSim* knots, int32_t first_knot, int32_t what, void* knot_obs_dev, int nsteps,
+                                 const void* weights_dev, int32_t period, int32_t first_slot, int32_t flags, const void* sigma_dev,
+                                 uint32_t salt, void* return_dev, int32_t* length_dev, void* obs_dev, void* reward_dev, uint8_t* done_dev,
+                                 void* term_obs_dev, uint16_t* reason_dev, void* action_dev, void* noise_dev, void* stream) {
+  PolicyCall call{"os2rr_rollout_policy_recorded", nsteps, weights_dev,
+                  flags & ~(OS2R_POLICY_PER_ENV | OS2R_POLICY_TANH | OS2R_POLICY_FIRST_EPISODE | OS2R_POLICY_SIGMA_PER_ENV |
+                            OS2R_POLICY_CLOCK_EPISODE | OS2R_POLICY_SCHEDULE_WRAP)};
+  call.scheduled = true; call.period = period; call.first_slot = first_slot;
+  call.sigma = sigma_dev; call.salt = salt; call.noise = noise_dev;
+  if (int rc = check_policy_call(sim, call)) return rc;
+  auto refuse = [&](const std::string& why) { sim->err = "os2rr_rollout_policy_recorded: " + why; return (int)OS2R_ERR_INVALID; };
+  if (!knots && !knot_obs_dev) return refuse("nothing to record into (knots and knot_obs_dev are both null)");
+  if (knots) {
+    if (knots == sim) return refuse("knots must be another handle than sim");
+    if (knots->cfg.dtype != sim->cfg.dtype) return refuse("sim and knots differ in dtype");
+    if (knots->cfg.device != sim->cfg.device) return refuse("sim and knots are on different devices");
+    if (!os2r::same_model(sim->cfg.model, knots->cfg.model)) return refuse("sim and knots are different robot models");
+    if (what == 0) return refuse("nothing selected (what == 0)");
+    if (what & ~(OS2R_COPY_STATE | OS2R_COPY_PARAMS)) return refuse("unknown bits in what");
+    if (first_knot < 0) return refuse("first_knot must be >= 0");
+    const long long need = ((long long)first_knot + (long long)nsteps) * (long long)sim->cfg.num_envs;
+    if (need > (long long)knots->cfg.num_envs)
+      return refuse("knots has " + std::to_string(knots->cfg.num_envs) + " environments, (first_knot + nsteps) * num_envs = " +
+                    std::to_string(need) + " are needed");
+  }
+  const KnotSink sink{knots, knots ? first_knot : 0, knots ? what : 0, knot_obs_dev};
+  DeviceGuard guard(sim->cfg.device);
+  return by_dtype(sim, [&](auto t) {
+    return do_rollout_policy<decltype(t)>(sim, nsteps, weights_dev, flags, return_dev, length_dev, obs_dev, reward_dev, done_dev, term_obs_dev,
+                                          reason_dev, (hipStream_t)stream, sigma_dev, salt, action_dev, noise_dev, period, first_slot, &sink);
+  });
+}
+
 int os2r_copy_envs(Os2rSim* dst, Os2rSim* src, const int32_t* index_dev, int32_t what, void* obs_dev, void* stream) {
   if (!dst) { g_create_error = "os2r_copy_envs: null destination handle"; return OS2R_ERR_INVALID; }
   if (!src) { dst->err = "os2r_copy_envs: null source handle"; return OS2R_ERR_INVALID; }
@@ -1074,12 +1155,17 @@ int os2r_register_model_kernels(const Os2rModel* model, int32_t dtype, int32_t d
   found += fused;
   hipDeviceptr_t lay = nullptr;
   size_t lay_bytes = 0;
+  if (hipModuleGetGlobal(&lay, &lay_bytes, e.module, "os2r_jit_policy_knots") == hipSuccess)
+    for (int d = 0; d < 2; ++d)
+      if (hipModuleGetFunction(&e.fn_policy_rec[d], e.module, (std::string("os2r_jit_policy_rec_c1_d") + char('0' + d)).c_str()) != hipSuccess)
+        e.fn_policy_rec[d] = nullptr;
+  lay = nullptr; lay_bytes = 0;
   if (hipModuleGetGlobal(&lay, &lay_bytes, e.module, "os2r_jit_layout") == hipSuccess && lay_bytes >= 3 * sizeof(unsigned long long)) {
     unsigned long long v[3] = {};
     const bool read = hipMemcpy(v, lay, sizeof(v), hipMemcpyDeviceToHost) == hipSuccess;
     // an object that announces a layout has it folded into its fused kernels: one that cannot be read serves no handle
     if (read) { e.fused_kinds = v[0]; e.fused_srcs = v[1]; e.fused_dim = (int)v[2]; }
-    else if (fused) { found -= fused; for (int d = 0; d < 2; ++d) e.fn_rollout[d] = e.fn_policy[d] = nullptr; }
+    else if (fused) { found -= fused; for (int d = 0; d < 2; ++d) e.fn_rollout[d] = e.fn_policy[d] = e.fn_policy_rec[d] = nullptr; }
     if (read) {
       bool both = true;
       for (int d = 0; d < 2; ++d)
@@ -1183,5 +1269,10 @@ OS2R_API int os2r_debug_set_stamp_buffer(Os2rSim* sim, unsigned long long* buf_d
 #endif
 
 const char* os2r_last_error(Os2rSim* sim) { return sim ? sim->err.c_str() : g_create_error.c_str(); }
+
+// libos2r_record.so (include/os2r_record.h) is linked from these objects too and exports the os2rr_* functions only; there the
+// thread's handle-less error text is that library's own copy
+const char* os2rr_last_error(void) { return g_create_error.c_str(); }
+int os2rr_abi_version(void) { return OS2R_RECORD_ABI_VERSION; }
 
 }  // extern "C"

@@ -137,9 +137,19 @@ static int launch_policy_rollout(const PolicyArgs<T>& p, hipStream_t s) {
   const StepArgs<T>& a = p.s;
   if (MD::CMASK == 0u || a.counters || !is_std_solver<T>(a.pgs_iters, a.pgs_normal_iters, a.pgs_exact, MD::NQ)) return 2;
   const dim3 grid((unsigned)((a.N + kWave - 1) / kWave)), block(kWave);
-  if (layout_is<LayA>(a)) { hipLaunchKernelGGL((policy_rollout_kernel<T, MD, true, DR, LayA>), grid, block, 0, s, p); return 0; }
+  // (os2rr_rollout_policy_recorded: a sink in the arguments takes the recording variant)
+  const bool record = p.knot_what != 0 || p.knot_obs != nullptr;
+  if (layout_is<LayA>(a)) {
+    if (record) hipLaunchKernelGGL((policy_record_kernel<T, MD, true, DR, LayA>), grid, block, 0, s, p);
+    else hipLaunchKernelGGL((policy_rollout_kernel<T, MD, true, DR, LayA>), grid, block, 0, s, p);
+    return 0;
+  }
 #if OS2R_UNIT == 1
-  if (layout_is<LayB>(a)) { hipLaunchKernelGGL((policy_rollout_kernel<T, MD, true, DR, LayB>), grid, block, 0, s, p); return 0; }
+  if (layout_is<LayB>(a)) {
+    if (record) hipLaunchKernelGGL((policy_record_kernel<T, MD, true, DR, LayB>), grid, block, 0, s, p);
+    else hipLaunchKernelGGL((policy_rollout_kernel<T, MD, true, DR, LayB>), grid, block, 0, s, p);
+    return 0;
+  }
 #endif
   return 2;
 }

@@ -3,7 +3,8 @@
 //
 // gym_os2r_amd/jit.py compiles this file once per kind, with the flags and the generated table of the step object plus
 //   -DOS2R_JIT_KIND=1   fused rollout:        os2r_jit_rollout_c1_d{0,1}
-//   -DOS2R_JIT_KIND=2   fused policy rollout: os2r_jit_policy_c1_d{0,1}
+//   -DOS2R_JIT_KIND=2   fused policy rollout: os2r_jit_policy_c1_d{0,1}, and os2r_jit_policy_rec_c1_d{0,1} with the data symbol
+//                       os2r_jit_policy_knots: the variants that record the knots (os2rr_rollout_policy_recorded)
 //   -DOS2R_JIT_KIND=3   linearize:            os2r_jit_lin_c{C}_d{0,1} and ..._s, C = OS2R_JIT_CONTACT
 // one kind per code object, so that the objects build side by side and the first use of a robot waits for the slowest of
 // them, not for their sum.  Every kernel wraps a device template of os2r_kernels.hpp as it is: the arithmetic of a step is
@@ -59,6 +60,16 @@ OS2R_JIT_ROLLOUT_KERNEL(os2r_jit_rollout_c1_d1, true)
     os2r::step_body<os2r::JitReal, os2r::JitModel, true, DR, true, os2r::JitLayout, false, os2r::kJitSolverStd, true,  \
                     true>(P.s);                                                                                        \
   }
+// the _rec kernels read the sink of os2rr_rollout_policy_recorded (the fields appended to PolicyArgs): announced, because a kernel
+// built without them would take the arguments and record nothing (os2r_register_model_kernels, include/os2r.h)
+extern "C" __device__ __attribute__((used)) const unsigned int os2r_jit_policy_knots = 1u;
+#define OS2R_JIT_POLICY_REC_KERNEL(NAME, DR)                                                                           \
+  extern "C" __global__ OS2R_STEP_KERNEL_ATTRS(OS2R_REAL) void NAME(const os2r::PolicyArgs<os2r::JitReal> P) {         \
+    os2r::step_body<os2r::JitReal, os2r::JitModel, true, DR, true, os2r::JitLayout, false, os2r::kJitSolverStd, true,  \
+                    true, true>(P.s);                                                                                  \
+  }
+OS2R_JIT_POLICY_REC_KERNEL(os2r_jit_policy_rec_c1_d0, false)
+OS2R_JIT_POLICY_REC_KERNEL(os2r_jit_policy_rec_c1_d1, true)
 OS2R_JIT_POLICY_KERNEL(os2r_jit_policy_c1_d0, false)
 OS2R_JIT_POLICY_KERNEL(os2r_jit_policy_c1_d1, true)
 #endif

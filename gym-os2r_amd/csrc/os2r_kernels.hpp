@@ -404,6 +404,25 @@ struct PolicyArgs {
   // os2r_rollout_policy_scheduled (appended likewise)
   int period;                    // 0: no schedule, w is one set; T >= 1: w is [T] sets, one per slot
   int first_slot;                // the clock's offset: the fused kernel adds its step index k, the launch loop's host has added it
+  // os2rr_rollout_policy_recorded (appended likewise): the sink of the knots.  At the top of env-step k environment e goes to lane
+  // knot_lane + k * N + e of another handle, whose arrays are [rows][knot_stride]: the row bases below are that handle's own
+  int knot_what;                 // OS2R_COPY_* bits; 0: no handle to record into
+  long long knot_stride;         // the destination's num_envs
+  long long knot_lane;           // first_knot * N (launch loop: (first_knot + k) * N is in the copy launch, this stays unused)
+  T* __restrict__ kq;            // OS2R_COPY_STATE: [nq][stride]
+  T* __restrict__ kqd;           // [nq][stride]
+  T* __restrict__ khist;         // [4][stride]
+  T* __restrict__ ksolver_l;     // [4 nq][stride]
+  uint32_t* __restrict__ ksolver_flags;
+  int32_t* __restrict__ ksteps;
+  uint32_t* __restrict__ kepisode;
+  uint8_t* __restrict__ kpose;
+  T* __restrict__ kmass_scale;   // OS2R_COPY_PARAMS: [nq][stride] each, gravity [stride]
+  T* __restrict__ kdamping;
+  T* __restrict__ kfriction;
+  T* __restrict__ kmu;
+  T* __restrict__ kgravity;
+  T* __restrict__ knot_obs;      // nullable: the observation the policy evaluates, [K][N][D] (fused) / step k's [N][D] slice (launch loop)
 };
 
 // The one policy function of both paths (fused rollout, launch loop).  Evaluation order is part of the contract
@@ -525,6 +544,66 @@ __device__ __forceinline__ void policy_action(const PolicyArgs<T>* P, const Step
   ay = z[1];
 }
 
+// os2rr_rollout_policy_recorded, fused: `ROWS` rows of an SoA array from column e of the source ([rows][Ns]) to column `at` of the
+// sink ([rows][Nd]), memory to memory: the loads of a group are issued ahead of its stores (copy_envs_kernel's kCopyGroup), the
+// registers live for the group only.  Tail lanes load the environment they shadow and store nothing.
+constexpr int kKnotGroup = 8;
+template <typename T, int ROWS>
+__device__ __forceinline__ void knot_rows(const T* __restrict__ src, long long Ns, long long e, T* __restrict__ dst, long long Nd,
+                                          long long at, bool valid) {
+#pragma unroll
+  for (int r0 = 0; r0 < ROWS; r0 += kKnotGroup) {
+    T v[kKnotGroup];
+#pragma unroll
+    for (int k = 0; k < kKnotGroup; ++k)
+      if (r0 + k < ROWS) v[k] = src[(long long)(r0 + k) * Ns + e];
+    if (valid) {
+#pragma unroll
+      for (int k = 0; k < kKnotGroup; ++k)
+        if (r0 + k < ROWS) dst[(long long)(r0 + k) * Nd + at] = v[k];
+    }
+  }
+}
+
+// Environment e as it stands at the top of env-step k -- q and qd in the registers just loaded, everything else in the arrays the
+// previous env-step (or launch) left -- becomes lane knot_lane + k N + e of the sink: the rows os2r_copy_envs moves for `what`,
+// all 4 nq solver rows among them (also the ones this kernel does not load: the copy is exact for impulses it does not remember,
+// and in fp32, where they are carried unused).  What this lane reads here it has written itself, one env-step earlier, in program
+// order; nothing reads the sink in this launch.
+template <typename T, int NQ>
+__device__ __forceinline__ void record_knot(const PolicyArgs<T>* P, const StepArgs<T>& A, long long e, bool valid, int k,
+                                            const T (&q)[NQ], const T (&qd)[NQ]) {
+  const int what = P->knot_what;
+  const long long Nd = P->knot_stride, at = P->knot_lane + (long long)k * A.N + e;
+  if (what & OS2R_COPY_STATE) {
+    if (valid) {
+#pragma unroll
+      for (int i = 0; i < NQ; ++i) {
+        P->kq[i * Nd + at] = q[i];
+        P->kqd[i * Nd + at] = qd[i];
+      }
+    }
+    knot_rows<T, 4>(A.hist, A.N, e, P->khist, Nd, at, valid);
+    knot_rows<T, 4 * NQ>(A.solver_l, A.N, e, P->ksolver_l, Nd, at, valid);
+    const uint32_t fl = A.solver_flags[e], ep = A.episode[e];
+    const int32_t st = A.steps[e];
+    const uint8_t po = A.pose[e];
+    if (valid) {
+      P->ksolver_flags[at] = fl;
+      P->ksteps[at] = st;
+      P->kepisode[at] = ep;
+      P->kpose[at] = po;
+    }
+  }
+  if (what & OS2R_COPY_PARAMS) {
+    knot_rows<T, NQ>(A.mass_scale, A.N, e, P->kmass_scale, Nd, at, valid);
+    knot_rows<T, NQ>(A.damping, A.N, e, P->kdamping, Nd, at, valid);
+    knot_rows<T, NQ>(A.friction, A.N, e, P->kfriction, Nd, at, valid);
+    knot_rows<T, NQ>(A.mu, A.N, e, P->kmu, Nd, at, valid);
+    knot_rows<T, 1>(A.gravity, A.N, e, P->kgravity, Nd, at, valid);
+  }
+}
+
 // ----------------------------------------------------------------------------------------
 // env-step kernel: GazeboRuntime.step (runtimes/gazebo_runtime.py:65-97) for every env
 // ----------------------------------------------------------------------------------------
@@ -565,10 +644,15 @@ constexpr int std_solver(bool std_sweeps, bool is_f64, bool std_exact) {
 // POLICY (with ROLLOUT; os2r_rollout_policy): the kernel's argument is a PolicyArgs; each step's action is the linear policy of
 // the observation the environment's previous step returned -- recomputed from the state the step loads anyway -- and the
 // owning lane adds the step's reward and count to the environment's return and length.
+// RECORD (with POLICY; os2rr_rollout_policy_recorded): at the top of every env-step the environment goes to the sink named in the
+// PolicyArgs.  A variant of its own (policy_record_kernel): as a run-time branch of the POLICY kernels it cost calls that record
+// nothing 1.4 - 3 % of their rate.
 template <typename T, typename MD, bool CONTACT, bool DR, bool STD_SWEEPS = false, typename LAY = RtLayout, bool COUNT = false,
-          int SOLVER = std_solver(STD_SWEEPS, sizeof(T) == 8, StdSolver<T>::kExact), bool ROLLOUT = false, bool POLICY = false>
+          int SOLVER = std_solver(STD_SWEEPS, sizeof(T) == 8, StdSolver<T>::kExact), bool ROLLOUT = false, bool POLICY = false,
+          bool RECORD = false>
 __device__ __forceinline__ void step_body(const StepArgs<T>& A) {
   static_assert(!POLICY || ROLLOUT, "the policy runs in the fused rollout");
+  static_assert(!RECORD || POLICY, "the knots are recorded by the policy rollout");
   constexpr int NQ = MD::NQ;
   // run-time models scan a wave-shared LDS copy of the candidate table; the compiled-in ones read the
   // (wave-uniform) coordinates through scalar loads, straight into the operands of the scan
@@ -650,11 +734,29 @@ __device__ __forceinline__ void step_body(const StepArgs<T>& A) {
       // the observation the previous step (or reset) returned: observe() of the stored state, as reset_kernel makes it
       // (the weights are loaded here and are dead before the physics iterations)
       const PolicyArgs<T>* pa = (const PolicyArgs<T>*)__builtin_amdgcn_kernarg_segment_ptr();
+      // os2rr_rollout_policy_recorded: the environment as it stands here goes to the sink, before anything of the step is formed
+      // (a wave-uniform test of a kernel argument; the sink's pointers are read from the argument segment here, step by step,
+      // and are dead before the physics iterations, like the weights)
+      if constexpr (RECORD) {
+        if (pa->knot_what != 0) {
+          const PolicyArgs<T>* pk = pa;
+          asm volatile("" : "+s"(pk));
+          record_knot<T, NQ>(pk, A, e, valid, k, q, qd);
+        }
+      }
       const T h2x = A.hist[2 * A.N + e], h2y = A.hist[3 * A.N + e];
       T o[OS2R_MAX_OBS];
       bool dn0;
       unsigned why0;
       observe<T, NQ, LAY>(ts, q, qd, h2x, h2y, o, dn0, why0);
+      if constexpr (RECORD) {
+        if (pa->knot_obs) {
+          // ... and the observation the policy is about to see, knot-major [K][N][D] (the tile is free until the physics iterations)
+          const PolicyArgs<T>* pk = pa;
+          asm volatile("" : "+s"(pk));
+          store_obs_tile<T>(pk->knot_obs + ko * D, o, D, e0, A.N, lane, tile);
+        }
+      }
       // (with sigma: the noise is drawn and a, eps of step k are stored here by the owning lane: nothing of it lives on)
       policy_action<T>(pa, A, D, e, valid, step_count, k, ko + e, o, ax, ay);
     } else if (A.actions) {
@@ -862,6 +964,12 @@ __global__ OS2R_STEP_KERNEL_ATTRS(T) void policy_rollout_kernel(const PolicyArgs
   step_body<T, MD, CONTACT, DR, true, LAY, false, std_solver(true, sizeof(T) == 8, StdSolver<T>::kExact), true, true>(P.s);
 }
 
+// os2rr_rollout_policy_recorded, fused: the same kernel with the sink in its step loop, under a name of its own
+template <typename T, typename MD, bool CONTACT, bool DR, typename LAY>
+__global__ OS2R_STEP_KERNEL_ATTRS(T) void policy_record_kernel(const PolicyArgs<T> P) {
+  step_body<T, MD, CONTACT, DR, true, LAY, false, std_solver(true, sizeof(T) == 8, StdSolver<T>::kExact), true, true, true>(P.s);
+}
+
 // os2r_rollout_policy, launch loop (the configurations without a fused variant): per env-step this kernel turns the stored state
 // into the observation and the policy's actions ([N][2], P.act), the step launch takes them, policy_accumulate_kernel sums.
 template <typename T, int NQ>
@@ -883,6 +991,10 @@ __global__ __launch_bounds__(kWave) void policy_kernel(const PolicyArgs<T> P) {
   bool dn;
   unsigned why;
   observe<T, NQ>(ts, q, qd, h2x, h2y, obs, dn, why);
+  if (P.knot_obs) {   // os2rr_rollout_policy_recorded: this env-step's [N][D] slice of the knots' observations
+    __shared__ T tile[kWave * OS2R_MAX_OBS];
+    store_obs_tile<T>(P.knot_obs, obs, ts->obs_dim, e0, A.N, lane, tile);
+  }
   T ax, ay;
   policy_action<T>(&P, A, ts->obs_dim, e, valid, A.step_count, 0, e, obs, ax, ay);
   if (valid) {

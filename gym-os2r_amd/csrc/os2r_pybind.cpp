@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/os2r.h"
+#include "../../include/os2r_record.h"
 
 namespace py = pybind11;
 using addr = std::uintptr_t;
@@ -91,5 +92,8 @@ PYBIND11_MODULE(_os2r_py, m) {
   m.def("get_violation_mirror", [](addr h) { const volatile uint32_t* w = nullptr; int rc = os2r_get_violation_mirror(H(h), &w); return py::make_tuple(rc, (addr)w); });
   m.def("register_model_kernels", [](addr model, int dtype, int device, const std::string& path) {
     return os2r_register_model_kernels((const Os2rModel*)P(model), dtype, device, path.c_str()); });
+  // libos2r_record.so (include/os2r_record.h)
+  bind(m, "rollout_policy_recorded", &os2rr_rollout_policy_recorded);
+  m.def("record_last_error", []() { return std::string(os2rr_last_error()); });
   m.def("last_error", [](addr h) { return std::string(os2r_last_error(H(h))); });
 }

@@ -202,9 +202,52 @@ class HipSim:
         # the kernel's layout per environment: [T][2][D+1][N], env index fastest
         return (weights.movedim(0, -1) if per_env else weights).contiguous(), abi.POLICY_PER_ENV if per_env else 0, T
 
+    def _knot_args(self, K, knots, first_knot, knot_state, knot_params, want_knot_obs):
+        """The recording keywords of rollout_schedule / rollout_policy -> None when none of them is used (the call is then the one
+        it always was), else (knots handle or None, first_knot, what); everything that needs no device is refused here."""
+        if knots is None and first_knot == 0 and knot_state is True and knot_params is True and not want_knot_obs:
+            return None
+        name = "rollout_schedule"
+        if knots is None:
+            if not want_knot_obs:
+                raise ValueError(f"{name}: first_knot, knot_state and knot_params need a knots handle (or want_knot_obs)")
+            return None, 0, 0
+        if not isinstance(knots, HipSim):
+            raise ValueError(f"{name}: knots must be a HipSim, got {type(knots)}")
+        if knots is self:
+            raise ValueError(f"{name}: knots must be another handle than the one that rolls out")
+        if knots.dtype != self.dtype or knots.device != self.device:
+            raise ValueError(f"{name}: knots must be {self.dtype} on {self.device}, got {knots.dtype} on {knots.device}")
+        if isinstance(first_knot, bool) or not isinstance(first_knot, int) or not 0 <= first_knot < 2 ** 31:
+            raise ValueError(f"{name}: first_knot must be a non-negative 32-bit integer, got {first_knot!r}")
+        if not knot_state and not knot_params:
+            raise ValueError(f"{name}: nothing to record (knot_state and knot_params are both off)")
+        if (first_knot + K) * self.N > knots.N:
+            raise ValueError(f"{name}: knots has {knots.N} environments, (first_knot + nsteps) * N = {(first_knot + K) * self.N} are needed")
+        return knots, first_knot, (abi.COPY_STATE if knot_state else 0) | (abi.COPY_PARAMS if knot_params else 0)
+
+    def _recorded(self, rec, want_knot_obs, K, w, T, first_slot, flags, sg, salt, ret, length, outs, act, eps):
+        """os2rr_rollout_policy_recorded (include/os2r_record.h: the companion library libos2r_record.so, or the pybind11 module,
+        which links it) with the arguments of the scheduled call behind the sink's; -> knot_obs [K, N, D] | None"""
+        call = getattr(self._lib, "os2rr_rollout_policy_recorded", None)
+        if call is None:
+            try:
+                call = _lib.load_record().os2rr_rollout_policy_recorded
+            except (ImportError, OSError, AttributeError) as e:
+                raise Os2rError(f"no rollout can record its knots without libos2r_record.so: {e}") from e
+        knots, first_knot, what = rec
+        knot_obs = self._new(K, self.N, self.D) if want_knot_obs else None
+        obs, rew, done, term, why = outs
+        self._check(call(
+            self._h, None if knots is None else knots._h, first_knot, what, _ptr(knot_obs), K, _ptr(w), T, int(first_slot), flags,
+            _ptr(sg), salt, _ptr(ret), _ptr(length), _ptr(obs), _ptr(rew), _ptr(done), _ptr(term), _ptr(why), _ptr(act), _ptr(eps),
+            self._stream()), "os2rr_rollout_policy_recorded")
+        return knot_obs
+
     def rollout_policy(self, nsteps: int, weights, *, tanh: bool = False, first_episode: bool = False, want_outputs: bool = False,
                        want_terminal: bool = False, want_reasons: bool = False, sigma=None, salt: int = 0,
-                       want_actions: bool = False, want_noise: bool = False):
+                       want_actions: bool = False, want_noise: bool = False, knots: Optional["HipSim"] = None, first_knot: int = 0,
+                       knot_state: bool = True, knot_params: bool = True, want_knot_obs: bool = False):
         """`nsteps` env-steps with the linear policy a = squash(W.o + b) in the loop, evaluated on the device on every environment's
         own observation (include/os2r.h: os2r_rollout_policy; one launch where os2r_rollout has a fused kernel).
         weights: [2, D+1] shared by all environments or [N, 2, D+1] one set per environment; row j (0 hip, 1 knee) holds
@@ -214,16 +257,26 @@ class HipSim:
         sigma (a float, a [2] tensor or an [N, 2] tensor in the handle's dtype): Gaussian exploration noise, a = squash(W.o + b +
         sigma * eps) with eps ~ N(0, 1) a pure function of (seed, global env index, step counter, salt) (include/os2r.h:
         os2r_rollout_policy_noisy); the call then returns a fourth element (actions [K, N, 2] if want_actions else None,
-        noise eps [K, N, 2] if want_noise else None): rollout(K, actions) replays the window bit for bit."""
+        noise eps [K, N, 2] if want_noise else None): rollout(K, actions) replays the window bit for bit.
+        knots, first_knot, knot_state, knot_params, want_knot_obs: the recording of rollout_schedule
+        (include/os2r_record.h: os2rr_rollout_policy_recorded with period = 1); with any of them the call returns one more element,
+        knot_obs [K, N, D] | None,
+        behind the (actions, noise) pair, which is then there without sigma too (as (None, None))."""
         K = int(nsteps)
         if K < 1:
             raise ValueError("rollout_policy: nsteps must be >= 1")
+        rec = self._knot_args(K, knots, first_knot, knot_state, knot_params, want_knot_obs)
         sg, sg_flags, salt = self._noise_args("rollout_policy", sigma, salt, want_actions=want_actions, want_noise=want_noise)
         w, per_env, _ = self._policy_weights("rollout_policy", weights, table=False)
         flags = (abi.POLICY_TANH if tanh else 0) | (abi.POLICY_FIRST_EPISODE if first_episode else 0) | per_env
         ret, length = self._new(self.N), self._new(self.N, dtype=torch.int32)
         outs = self._steps_out(K, want_terminal, want_reasons) if want_outputs else (None,) * 5
         obs, rew, done, term, why = outs
+        if rec is not None:
+            act = self._new(K, self.N, 2) if want_actions else None
+            eps = self._new(K, self.N, 2) if want_noise else None
+            knot_obs = self._recorded(rec, want_knot_obs, K, w, 1, 0, flags | sg_flags, sg, salt, ret, length, outs, act, eps)
+            return ret, length, (outs if want_outputs else None), (act, eps), knot_obs
         if sg is not None:
             act = self._new(K, self.N, 2) if want_actions else None
             eps = self._new(K, self.N, 2) if want_noise else None
@@ -238,7 +291,8 @@ class HipSim:
     def rollout_schedule(self, nsteps: int, weights, *, clock: str = "window", wrap: bool = False, first_slot: int = 0,
                          tanh: bool = False, first_episode: bool = False, sigma=None, salt: int = 0, want_outputs: bool = False,
                          want_terminal: bool = False, want_reasons: bool = False, want_actions: bool = False,
-                         want_noise: bool = False):
+                         want_noise: bool = False, knots: Optional["HipSim"] = None, first_knot: int = 0, knot_state: bool = True,
+                         knot_params: bool = True, want_knot_obs: bool = False):
         """`nsteps` env-steps with a time-scheduled linear policy in the loop (include/os2r.h: os2r_rollout_policy_scheduled; one
         launch where os2r_rollout has a fused kernel): a table of T weight sets, each as rollout_policy takes one, of which every
         environment evaluates the set of its slot in each env-step.
@@ -249,7 +303,15 @@ class HipSim:
         K steps equal K1 steps followed by K - K1 steps with first_slot + K1, bit for bit.
         sigma, salt, want_noise: the exploration noise of rollout_policy.  want_actions works with and without sigma:
         rollout(K, actions) replays the window bit for bit.
-        -> (returns [N], lengths [N] int32, outputs | None, (actions [K, N, 2] | None, noise [K, N, 2] | None))."""
+        knots (include/os2r_record.h: os2rr_rollout_policy_recorded; the same launch): another HipSim of the same dtype, device and robot
+        with at least (first_knot + K) N environments; at the top of env-step k, before the action is formed, environment e -- after
+        its reset, if the previous env-step auto-reset it -- becomes environment (first_knot + k) N + e of `knots`, exactly as
+        knots.copy_envs_from(self, index, state=knot_state, params=knot_params) would copy it; every other environment of `knots`
+        stays as it is.  knots.linearize then returns the Jacobians of every knot, knot-major.  first_knot splits a window as
+        first_slot does.  want_knot_obs: the observation the policy evaluates at the top of each env-step, [K, N, D]: the `obs` of
+        lqr_gains / ilqr_backward as [K N, D], with or without `knots`.
+        -> (returns [N], lengths [N] int32, outputs | None, (actions [K, N, 2] | None, noise [K, N, 2] | None)), and with any of the
+        recording keywords one more element: knot_obs [K, N, D] | None."""
         K = int(nsteps)
         if K < 1:
             raise ValueError("rollout_schedule: nsteps must be >= 1")
@@ -258,6 +320,7 @@ class HipSim:
         if not 0 <= int(first_slot) < 2 ** 31:
             raise ValueError("rollout_schedule: first_slot must be a non-negative 32-bit value")
         sg, sg_flags, salt = self._noise_args("rollout_schedule", sigma, salt, want_noise=want_noise)
+        rec = self._knot_args(K, knots, first_knot, knot_state, knot_params, want_knot_obs)
         w, per_env, T = self._policy_weights("rollout_schedule", weights, table=True)
         flags = ((abi.POLICY_TANH if tanh else 0) | (abi.POLICY_FIRST_EPISODE if first_episode else 0) | per_env |
                  (abi.POLICY_CLOCK_EPISODE if clock == "episode" else 0) | (abi.POLICY_SCHEDULE_WRAP if wrap else 0))
@@ -266,6 +329,9 @@ class HipSim:
         obs, rew, done, term, why = outs
         act = self._new(K, self.N, 2) if want_actions else None
         eps = self._new(K, self.N, 2) if want_noise else None
+        if rec is not None:
+            knot_obs = self._recorded(rec, want_knot_obs, K, w, T, first_slot, flags | sg_flags, sg, salt, ret, length, outs, act, eps)
+            return ret, length, (outs if want_outputs else None), (act, eps), knot_obs
         self._check(self._lib.os2r_rollout_policy_scheduled(self._h, K, _ptr(w), T, int(first_slot), flags | sg_flags, _ptr(sg), salt,
                                                             _ptr(ret), _ptr(length), _ptr(obs), _ptr(rew), _ptr(done), _ptr(term),
                                                             _ptr(why), _ptr(act), _ptr(eps), self._stream()),

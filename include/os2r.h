@@ -356,7 +356,12 @@ OS2R_API int os2r_rollout_policy_scheduled(Os2rSim* sim, int nsteps, const void*
  * The first two serve handles with ground contact, the default solver settings and no work
  * counters -- where the compiled-in robots have a fused variant; every other handle keeps its
  * launch loop.  If their object carries os2r_jit_layout they have that layout folded in and
- * serve handles of that layout only; without the symbol they serve any layout.  An object is
+ * serve handles of that layout only; without the symbol they serve any layout.  A policy object
+ * may also export os2r_jit_policy_rec_c1_d{0,1}, the policy kernels that read the sink of
+ * os2rr_rollout_policy_recorded of include/os2r_record.h (the fields appended to their argument), together with the data
+ * symbol os2r_jit_policy_knots that announces them; on a handle whose policy object lacks the
+ * symbol or the kernels -- hand-built, or built before the sink existed: its kernels would take
+ * the arguments and record nothing -- a recorded call takes the launch loop.  An object is
  * accepted if it exports at least one kernel named in this comment.  A handle keeps what was
  * registered when it was created.
  * Errors: os2r_last_error(NULL).                                                            */
