@@ -3,7 +3,7 @@
 by side towards a target posture, the backward pass in one os2rc_ilqr_backward launch.
 
   python examples/ilqr_balancing.py [--envs 64] [--steps 40] [--iters 10] [--settle 300] [--perturb 0.05] [--mu 0.0] [--eps 1e-4]
-                                    [--knots recorded|loop]
+                                    [--knots recorded|loop] [--line-search torch|device]
 
 The cost of a trajectory is sum_k 1/2 (x_k - x*)'Q(x_k - x*) + 1/2 a_k'R a_k plus 1/2 (x_K - x*)'Q(x_K - x*), read off the raw
 observation slots (state components the task does not observe carry no weight); x* is the posture the PD of lqr_balancing.py
@@ -26,6 +26,14 @@ of what that launch returned.  An iteration is five launches: linearize, ilqr_ba
 rollout_schedule, copy_envs_from (the accepted knots).  The first nominal comes from one recorded rollout whose table has zero
 gains and the actions as bias.  Both modes visit the same states bit for bit and print the same costs (as long as no episode ends
 inside a trajectory: an auto-reset draws from the lane's own random stream, and a candidate's lane is not the nominal's).
+With --line-search device (needs --knots recorded) steps 3, 6 and 7 are one os2rs_ilqr_line_search launch
+(HipSim.ilqr_line_search): it scores every candidate, accepts a step size PER TRAJECTORY, updates the nominal in place where one
+was accepted -- actions, knot observations, cost, and lx, lu, p_final in the layout the backward pass reads -- and returns the
+index with which one copy_envs_from moves exactly the accepted knots.  An iteration is then six launches with no tensor
+reshuffled in between; the host reads back one flag, (choice >= 0).any(), to steer mu (raised only when no trajectory accepted
+anything), and for its printed line the mean cost and how many trajectories took which step size.  The first nominal is
+initialised by the same call with one candidate per trajectory.  The default, --line-search torch, is the iteration above with
+one step size for the whole batch.
 Printed per iteration: the cost (mean over the trajectories), the step size, mu, the refused knots, and the predicted against
 the actual change.  The script prints what happened; it claims no control quality: a quotient across a change of contact mode
 is a secant, the default eps is not tuned, and the actions saturate, which the model knows nothing about.
@@ -59,9 +67,14 @@ def main():
     ap.add_argument("--knots", choices=("recorded", "loop"), default="recorded",
                     help="recorded: the candidates' rollout records the knots (five launches per iteration); loop: the nominal is "
                          "replayed and forked knot by knot")
+    ap.add_argument("--line-search", choices=("torch", "device"), default="torch",
+                    help="torch: costs and one step size for the whole batch in torch; device: one os2rs_ilqr_line_search launch, a step "
+                         "size per trajectory (needs --knots recorded)")
     args = ap.parse_args()
     M, K, nal = args.envs, args.steps, len(ALPHAS)
     recorded = args.knots == "recorded"
+    if args.line_search == "device" and not recorded:
+        ap.error("--line-search device needs --knots recorded")
     # one task, three handles: the nominal (M trajectories), the knots (K M lanes, knot-major), the candidates (4 M environments);
     # recorded: a fourth for the knots of every candidate (K 4 M lanes, knot-major)
     envs = [g.make("Monopod-nonorm-balance-v1", num_envs=n, seed=args.seed) for n in (M, K * M, nal * M) + ((K * nal * M,) if recorded else ())]
@@ -85,7 +98,8 @@ def main():
         K_pd[:, j, dof] = args.kp / 2.5
         K_pd[:, j, nq + dof] = args.kd / 2.5
     nom.rollout_policy(args.settle, weights_of_gain(K_pd, torch.zeros(M, 2, dtype=dt, device=dev), obs0, cols))
-    target = nom.copy_envs_from(nom, want_obs=True)[:, slots]                         # [M, raw slots]
+    target_obs = nom.copy_envs_from(nom, want_obs=True)                               # [M, D]
+    target = target_obs[:, slots]                                                     # [M, raw slots]
     q, qd = nom.get_state()
     gen = torch.Generator(device=dev).manual_seed(args.seed + 1)
     observed = torch.tensor([c in shown for c in range(n)], dtype=dt, device=dev)
@@ -108,6 +122,11 @@ def main():
     first = torch.arange(M, dtype=torch.int32, device=dev).repeat(nal)                # knot 0 of trajectory m, once per step size
     U = torch.zeros(K, M, 2, dtype=dt, device=dev)
     mu, it, tries, shown_cost = args.mu, 0, 0, None
+    if args.line_search == "device":
+        line_search_on_device(args, nom, knots, cand, cand_knots, start, target_obs, Q.cpu(), R.cpu(), first)
+        for e in envs:
+            e.close()
+        return
     if recorded:
         # the first nominal, recorded: zero gains, the actions as bias (b + 0 o = b: the open-loop actions, bit for bit)
         table0 = torch.zeros(M, K, 2, D + 1, dtype=dt, device=dev)
@@ -183,6 +202,55 @@ def main():
         print(f"iter {it:2d} cost {shown_cost:.6e} (no step size was accepted)", flush=True)
     for e in envs:
         e.close()
+
+
+def line_search_on_device(args, nom, knots, cand, cand_knots, start, target, Q, R, first):
+    """The iteration with HipSim.ilqr_line_search: linearize, ilqr_backward, copy_envs_from (knot 0 -> candidates),
+    rollout_schedule (recorded), ilqr_line_search, copy_envs_from (the accepted knots)."""
+    M, K, nal = args.envs, args.steps, len(ALPHAS)
+    dev, dt, D = nom.device, nom.dtype, nom.D
+    alphas = torch.tensor(ALPHAS, dtype=dt, device=dev)
+    # the first nominal, recorded: zero gains, zero bias; the line search with one candidate per trajectory initialises it
+    table0 = torch.zeros(M, K, 2, D + 1, dtype=dt, device=dev)
+    nom.restore(start)
+    _, _, (o_n, _, d_n, _, _), (a_n, _), kobs = nom.rollout_schedule(K, table0, want_outputs=True, want_actions=True, knots=knots,
+                                                                     want_knot_obs=True)
+    choice, _, _, nominal = nom.ilqr_line_search(kobs, o_n[K - 1], a_n, target, Q, R, done=d_n, want_cand_cost=False)
+    print(f"iter {0:2d} cost {float(nominal['cost'].mean()):.6e} (the nominal: zero torque; {int((choice < 0).sum())} of {M} trajectories "
+          f"had an episode end inside it and stay out)", flush=True)
+    a_k, obs_k = nominal["actions"].view(K * M, 2), nominal["obs"].view(K * M, D)        # views: updated in place by every call
+    mu, it, tries = args.mu, 0, 0
+    while it < args.iters and tries < 4 * args.iters:
+        tries += 1
+        _, _, A, B = knots.linearize(a_k, args.eps, want_next=False)
+        _, _, _, _, flags, dv, table = nom.ilqr_backward(A, B, Q, R, knots=K, lx=nominal["lx_view"], lu=nominal["lu_view"], mu=mu,
+                                                         p_final=nominal["p_final_view"], actions=a_k, obs=obs_k, alphas=ALPHAS,
+                                                         want_gains=False, want_ff=False, want_weights=True)
+        cand.copy_envs_from(knots, first)
+        _, _, (o_c, _, d_c, _, _), (a_c, _), kobs_c = cand.rollout_schedule(K, table, want_outputs=True, want_actions=True,
+                                                                          knots=cand_knots, want_knot_obs=True)
+        before = nominal["cost"].clone()
+        choice, index, _, _ = nom.ilqr_line_search(kobs_c, o_c[K - 1], a_c, target, Q, R, nominal=nominal, done=d_c, want_cand_cost=False)
+        knots.copy_envs_from(cand_knots, index)
+        accepted = bool((choice >= 0).any())                                          # the iteration's one decision on the host
+        # (what follows is read back for the printed line only)
+        took = torch.bincount(choice + 1, minlength=nal + 1).tolist()
+        refused = int(flags.sum())
+        if accepted:
+            it += 1
+            al = torch.where(choice >= 0, alphas[choice.clamp(min=0).long()], torch.zeros((), dtype=dt, device=dev))
+            predicted = float((al * dv[:, :, 0].sum(0) + al * al * dv[:, :, 1].sum(0)).sum()) / M
+            actual = float((nominal["cost"] - before).sum()) / M
+            steps = ", ".join(f"{took[i + 1]} x {ALPHAS[i]}" for i in range(nal))
+            print(f"iter {it:2d} cost {float(nominal['cost'].mean()):.6e} step sizes {steps}, none {took[0]}; mu {mu:.3e} refused {refused} of "
+                  f"{K * M} knots, predicted change {predicted:+.4e} actual {actual:+.4e}", flush=True)
+            mu = 0.5 * mu if mu > 1e-3 else 0.0
+        else:
+            print(f"        no trajectory accepted a step size at mu {mu:.3e} (refused {refused} of {K * M} knots): mu raised", flush=True)
+            mu = max(10.0 * mu, 0.1)
+    while it < args.iters:                                                            # (kept: every iteration has its line)
+        it += 1
+        print(f"iter {it:2d} cost {float(nominal['cost'].mean()):.6e} (no step size was accepted)", flush=True)
 
 
 if __name__ == "__main__":

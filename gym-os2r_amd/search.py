@@ -1,0 +1,56 @@
+"""Loader of ``libos2r_search.so`` (include/os2r_search.h), the companion library of ``libos2r.so`` and ``libos2r_control.so``
+for the forward-pass evaluation of iLQR: the cost of every line-search candidate, one accepted step size per trajectory and the
+nominal updated in place, in one launch.
+
+ctypes only, like gym_os2r_amd.control, whose Os2rControlLayout, layout() and slot_columns() it takes as they are: a line
+search is one call per iteration.  HipSim.ilqr_line_search uses this loader whichever binding drives ``libos2r.so``.  There is
+no fallback: if the library has not been built (``make -C gym-os2r_amd/csrc``), load() raises.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+
+from .control import MAX_ALPHAS, MAX_OBS, Os2rControlLayout, layout, slot_columns  # noqa: F401  (re-exported)
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.environ.get("OS2R_SEARCH_LIBRARY") or os.path.join(_HERE, "libos2r_search.so")
+_lib = None
+
+ABI_VERSION = 1          # OS2R_SEARCH_ABI_VERSION
+ACCEPT_ALWAYS = 1        # OS2RS_ACCEPT_ALWAYS
+
+_vp, _i32, _f64p = C.c_void_p, C.c_int32, C.POINTER(C.c_double)
+
+# Every entry point include/os2r_search.h declares, in the header's order, with its ctypes argument types: the library's one
+# declaration (tests/test_ilqr_line_search_host.py holds it against the header).  The result is c_int, except for
+# os2rs_last_error (c_char_p).
+ENTRY_POINTS = {
+    "os2rs_abi_version": (),
+    "os2rs_last_error": (),
+    "os2rs_ilqr_line_search": (C.POINTER(Os2rControlLayout), _i32, C.c_int64, _i32, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _f64p, _f64p, _f64p,
+                               _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp),
+}
+
+
+class Os2rSearchLibraryMissing(ImportError):
+    pass
+
+
+def load():
+    global _lib
+    if _lib is not None:
+        return _lib
+    if not os.path.exists(LIB_PATH):
+        raise Os2rSearchLibraryMissing(
+            f"{LIB_PATH} not found: build the HIP extension first (make -C gym-os2r_amd/csrc). There is no CPU fallback.")
+    import torch  # noqa: F401  (first, so that the process holds one HIP runtime: gym_os2r_amd._lib.load says why)
+    lib = C.CDLL(LIB_PATH)
+    for name, argtypes in ENTRY_POINTS.items():
+        fn = getattr(lib, name)  # AttributeError here means header and library disagree
+        fn.argtypes = list(argtypes)
+        fn.restype = C.c_char_p if name == "os2rs_last_error" else C.c_int
+    if lib.os2rs_abi_version() != ABI_VERSION:
+        raise ImportError("libos2r_search.so ABI version does not match gym_os2r_amd.search")
+    _lib = lib
+    return lib

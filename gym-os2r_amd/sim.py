@@ -813,6 +813,9 @@ class HipSim:
         def given(t, shape, name, perm):
             if t is None:
                 return None
+            if (isinstance(t, torch.Tensor) and t.dtype == self.dtype and t.device == self.device and tuple(t.shape) == tuple(shape)
+                    and t.permute(*perm).is_contiguous()):
+                return t.permute(*perm)          # a permuted view of the kernel's layout (ilqr_line_search's *_view): no copy
             try:
                 return self._in(t, shape).permute(*perm).contiguous()
             except ValueError as e:
@@ -836,6 +839,97 @@ class HipSim:
         return (gains.permute(0, 3, 1, 2) if want_gains else None, ff.permute(0, 2, 1) if want_ff else None,
                 pout.permute(2, 0, 1) if want_P else None, vout.permute(1, 0) if want_p else None, flags,
                 dv.permute(0, 2, 1) if want_dv else None, wts.permute(3, 0, 1, 2) if want_weights else None)
+
+    # -- iLQR line search ------------------------------------------------------------------
+    def ilqr_line_search_into(self, knot_obs, end_obs, actions, target, Q, R, *, cost, choice, done=None, Q_final=None, always=False,
+                              act_nom=None, obs_nom=None, end_nom=None, lx=None, lu=None, p_final=None, index=None, cand_cost=None):
+        """Allocation-free line search of iLQR on tensors in the kernel's layouts (include/os2r_search.h: os2rs_ilqr_line_search;
+        the arithmetic and its order are spelled out there).  With M trajectories (target [M, D]), N = nalpha M candidate lanes
+        (lane i M + m: trajectory m under step size i), K knots, L = K M and n = 2nq: knot_obs [K, N, D], end_obs [N, D],
+        actions [K, N, 2] and done [K, N] uint8 (or None) are what the candidates' recorded rollout returned; Q, R and Q_final
+        (None: Q) host values as in ilqr_backward.  The nominal, updated in place where a trajectory accepted a candidate and left
+        alone elsewhere: cost [M] (required; a candidate must lower it unless always=True), act_nom [K, M, 2], obs_nom [K, M, D],
+        end_nom [M, D], lx [n, L], lu [2, L], p_final [n, M] (the last three as ilqr_backward_into reads them), each or None.
+        Written on every call: choice [M] int32 (the accepted candidate or -1, required), index [L] int32 (what
+        copy_envs_from(cand_knots, index) takes on the K M-lane knots handle) and cand_cost [nalpha, M], each or None.  Shapes,
+        dtypes, device and contiguity are checked before the library is called (it takes addresses)."""
+        what = "ilqr_line_search"
+        n, D = 2 * self.nq, self.D
+        q, r = self._lqr_cost(Q, R, what)
+        qf = None if Q_final is None else self._lqr_cost(Q_final, R, f"{what}: Q_final")[0]
+        if not isinstance(target, torch.Tensor) or target.dim() != 2:
+            raise ValueError(f"{what}: target must be a tensor of shape (M, {D})")
+        if not isinstance(knot_obs, torch.Tensor) or knot_obs.dim() != 3:
+            raise ValueError(f"{what}: knot_obs must be a tensor of shape (K, nalpha * M, {D})")
+        M, K, N = int(target.shape[0]), int(knot_obs.shape[0]), int(knot_obs.shape[1])
+        if M < 1 or K < 1 or N < M or N % M:
+            raise ValueError(f"{what}: the {N} candidate lanes of knot_obs [{K} knots] are no multiple of the {M} trajectories of target")
+        nal, L = N // M, K * M
+        if not 1 <= nal <= 16:
+            raise ValueError(f"{what}: between 1 and 16 candidates per trajectory, got {nal}")
+        if K * N > 2 ** 31 - 1:
+            raise ValueError(f"{what}: {K} knots of {N} candidate lanes exceed what an int32 index addresses")
+        if cost is None or choice is None:
+            raise ValueError(f"{what}: cost and choice are required")
+        for t, shape, name in ((knot_obs, (K, N, D), "knot_obs"), (end_obs, (N, D), "end_obs"), (actions, (K, N, 2), "actions"),
+                               (target, (M, D), "target"), (cost, (M,), "cost"), (act_nom, (K, M, 2), "act_nom"),
+                               (obs_nom, (K, M, D), "obs_nom"), (end_nom, (M, D), "end_nom"), (lx, (n, L), "lx"), (lu, (2, L), "lu"),
+                               (p_final, (n, M), "p_final"), (cand_cost, (nal, M), "cand_cost")):
+            self._out(t, shape, self.dtype, f"{what}: {name}")
+        self._out(done, (K, N), torch.uint8, f"{what}: done")
+        self._out(choice, (M,), torch.int32, f"{what}: choice")
+        self._out(index, (L,), torch.int32, f"{what}: index")
+        if end_obs is None or actions is None:
+            raise ValueError(f"{what}: end_obs and actions are required")
+        from . import control, search
+        lib = search.load()
+        lay = self.__dict__.get("_control_layout")
+        if lay is None:       # filled once from the handle's config (shared with ilqr_backward)
+            lay = self._control_layout = control.layout(abi.F64 if self.dtype == torch.float64 else abi.F32, self.nq, self.cfg.device,
+                                                        control.slot_columns(self.cfg.task, self.nq))
+        rc = lib.os2rs_ilqr_line_search(C.byref(lay), K, M, nal, search.ACCEPT_ALWAYS if always else 0, _ptr(knot_obs), _ptr(end_obs),
+                                        _ptr(actions), _ptr(done), _ptr(target), q, r, qf, _ptr(cost), _ptr(act_nom), _ptr(obs_nom),
+                                        _ptr(end_nom), _ptr(lx), _ptr(lu), _ptr(p_final), _ptr(choice), _ptr(index), _ptr(cand_cost),
+                                        self._stream())
+        if rc != abi.OK:
+            raise Os2rError(f"os2rs_ilqr_line_search failed ({rc}): {lib.os2rs_last_error().decode()}")
+
+    def ilqr_line_search(self, knot_obs, end_obs, actions, target, Q, R, *, nominal=None, done=None, Q_final=None,
+                         want_cand_cost: bool = True):
+        """The line search of iLQR for M trajectories in one launch (include/os2r_search.h: os2rs_ilqr_line_search): the cost
+        sum_k 1/2 e_k'Q e_k + 1/2 a_k'R a_k + 1/2 e_K'Q_final e_K of every candidate, e the observation minus target on the raw
+        slots, one accepted step size per trajectory, and the nominal updated in place where a step was accepted.  knot_obs
+        [K, nalpha M, D], end_obs [nalpha M, D], actions [K, nalpha M, 2] and done [K, nalpha M] are what the candidates'
+        recorded rollout_schedule returned (knot observations, row K-1 of obs, applied actions, done), target [M, D].
+        nominal=None: a new nominal is allocated and every candidate with a finite cost and no episode end is acceptable (with
+        one candidate per trajectory, the first nominal's own rollout, this initialises it); a dict: the one an earlier call
+        returned, updated in place -- a candidate must lower its trajectory's cost.  The dict holds cost [M], actions [K, M, 2],
+        obs [K, M, D], end_obs [M, D], lx [n, K M], lu [2, K M], p_final [n, M] (the kernel's layouts) and lx_view [K M, n],
+        lu_view [K M, 2], p_final_view [M, n], permuted views ilqr_backward takes without a copy.
+        -> (choice [M] int32: the accepted candidate or -1, index [K M] int32 for knots.copy_envs_from(cand_knots, index),
+        cand_cost [nalpha, M] or None, nominal)."""
+        what = "ilqr_line_search"
+        if not isinstance(target, torch.Tensor) or target.dim() != 2 or not isinstance(knot_obs, torch.Tensor) or knot_obs.dim() != 3:
+            raise ValueError(f"{what}: target must be a tensor of shape (M, {self.D}) and knot_obs one of shape (K, nalpha * M, {self.D})")
+        M, K, N, n = int(target.shape[0]), int(knot_obs.shape[0]), int(knot_obs.shape[1]), 2 * self.nq
+        if M < 1 or K < 1 or N < M or N % M:
+            raise ValueError(f"{what}: the {N} candidate lanes of knot_obs [{K} knots] are no multiple of the {M} trajectories of target")
+        always = nominal is None
+        if always:
+            nominal = dict(cost=self._new(M), actions=self._new(K, M, 2), obs=self._new(K, M, self.D), end_obs=self._new(M, self.D),
+                           lx=self._new(n, K * M), lu=self._new(2, K * M), p_final=self._new(n, M))
+            for name in ("lx", "lu", "p_final"):
+                nominal[name + "_view"] = nominal[name].permute(1, 0)
+            for t in nominal.values():           # a trajectory none of whose candidates is acceptable keeps zeros, not garbage
+                t.zero_()
+        elif not isinstance(nominal, dict) or any(k not in nominal for k in ("cost", "actions", "obs", "end_obs", "lx", "lu", "p_final")):
+            raise ValueError(f"{what}: nominal must be None or the dict an earlier call returned")
+        choice, index = self._new(M, dtype=torch.int32), self._new(K * M, dtype=torch.int32)
+        cand_cost = self._new(N // M, M) if want_cand_cost else None
+        self.ilqr_line_search_into(knot_obs, end_obs, actions, target, Q, R, cost=nominal["cost"], choice=choice, done=done, Q_final=Q_final,
+                                   always=always, act_nom=nominal["actions"], obs_nom=nominal["obs"], end_nom=nominal["end_obs"],
+                                   lx=nominal["lx"], lu=nominal["lu"], p_final=nominal["p_final"], index=index, cand_cost=cand_cost)
+        return choice, index, cand_cost, nominal
 
     def action_violations_into(self, dst: torch.Tensor, clear: bool = True):
         """Copy the running count of out-of-range caller actions into ``dst`` (one int32/uint32 element,
