@@ -77,47 +77,45 @@ class Os2rLibraryMissing(ImportError):
     pass
 
 
-def load_record():
-    """libos2r_record.so through ctypes (after libos2r.so, and so after torch: one HIP runtime per process)."""
-    global _record
-    if _record is not None:
-        return _record
-    load()
-    if not os.path.exists(RECORD_LIB_PATH):
-        raise Os2rLibraryMissing(f"{RECORD_LIB_PATH} not found: it is built with libos2r.so (make -C gym-os2r_amd/csrc); without it "
-                                 "no rollout can record its knots")
-    lib = C.CDLL(RECORD_LIB_PATH)
-    for name, argtypes in RECORD_ENTRY_POINTS.items():
-        fn = getattr(lib, name)
-        fn.argtypes = list(argtypes)
-        fn.restype = C.c_char_p if name == "os2rr_last_error" else C.c_int
-    if lib.os2rr_abi_version() != RECORD_ABI_VERSION:
-        raise ImportError("libos2r_record.so ABI version does not match gym_os2r_amd._lib")
-    _record = lib
-    return lib
-
-
-def load():
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise Os2rLibraryMissing(
-            f"{LIB_PATH} not found: build the HIP extension first (make -C gym-os2r_amd/csrc). "
-            "The stepper has no CPU fallback.")
+def load_library(path, entry_points, last_error, version, missing, build_hint, mismatch):
+    """One C-ABI library through ctypes: argument and result types from its table of entry points (the result is c_int, c_char_p
+    for `last_error`), the ABI number `version` = (symbol, expected) checked.  A file that is not there raises
+    missing(f"{path} not found: {build_hint}"), another ABI ImportError(mismatch).  The four loaders keep what this returns."""
+    if not os.path.exists(path):
+        raise missing(f"{path} not found: {build_hint}")
     # torch first: the library needs libamdhip64, and the process must hold ONE HIP runtime -- the one torch brings.  Loaded before
     # torch (e.g. build() and smoke() of __graft_entry__ in one process) the library pulls in the system's runtime, torch then
     # its own, and os2r_create sees no device through the first ("no HIP device visible").
     import torch  # noqa: F401
-    lib = C.CDLL(LIB_PATH)
-    for name, argtypes in ENTRY_POINTS.items():
+    lib = C.CDLL(path)
+    for name, argtypes in entry_points.items():
         fn = getattr(lib, name)  # AttributeError here means header and library disagree
         fn.argtypes = list(argtypes)
-        fn.restype = C.c_char_p if name == "os2r_last_error" else C.c_int
-    if lib.os2r_abi_version() != abi.ABI_VERSION:
-        raise ImportError("libos2r.so ABI version does not match gym_os2r_amd.abi")
-    _lib = lib
+        fn.restype = C.c_char_p if name == last_error else C.c_int
+    symbol, expected = version
+    if getattr(lib, symbol)() != expected:
+        raise ImportError(mismatch)
     return lib
+
+
+def load_record():
+    """libos2r_record.so through ctypes (after libos2r.so, and so after torch: one HIP runtime per process)."""
+    global _record
+    if _record is None:
+        load()
+        _record = load_library(RECORD_LIB_PATH, RECORD_ENTRY_POINTS, "os2rr_last_error", ("os2rr_abi_version", RECORD_ABI_VERSION),
+                               Os2rLibraryMissing, "it is built with libos2r.so (make -C gym-os2r_amd/csrc); without it no rollout can "
+                               "record its knots", "libos2r_record.so ABI version does not match gym_os2r_amd._lib")
+    return _record
+
+
+def load():
+    global _lib
+    if _lib is None:
+        _lib = load_library(LIB_PATH, ENTRY_POINTS, "os2r_last_error", ("os2r_abi_version", abi.ABI_VERSION), Os2rLibraryMissing,
+                            "build the HIP extension first (make -C gym-os2r_amd/csrc). The stepper has no CPU fallback.",
+                            "libos2r.so ABI version does not match gym_os2r_amd.abi")
+    return _lib
 
 
 def _a(x):

@@ -11,6 +11,7 @@ import ctypes as C
 import os
 
 from . import abi
+from ._lib import load_library
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("OS2R_CONTROL_LIBRARY") or os.path.join(_HERE, "libos2r_control.so")
@@ -46,21 +47,11 @@ class Os2rControlLibraryMissing(ImportError):
 
 def load():
     global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise Os2rControlLibraryMissing(
-            f"{LIB_PATH} not found: build the HIP extension first (make -C gym-os2r_amd/csrc). There is no CPU fallback.")
-    import torch  # noqa: F401  (first, so that the process holds one HIP runtime: gym_os2r_amd._lib.load says why)
-    lib = C.CDLL(LIB_PATH)
-    for name, argtypes in ENTRY_POINTS.items():
-        fn = getattr(lib, name)  # AttributeError here means header and library disagree
-        fn.argtypes = list(argtypes)
-        fn.restype = C.c_char_p if name == "os2rc_last_error" else C.c_int
-    if lib.os2rc_abi_version() != ABI_VERSION:
-        raise ImportError("libos2r_control.so ABI version does not match gym_os2r_amd.control")
-    _lib = lib
-    return lib
+    if _lib is None:
+        _lib = load_library(LIB_PATH, ENTRY_POINTS, "os2rc_last_error", ("os2rc_abi_version", ABI_VERSION), Os2rControlLibraryMissing,
+                            "build the HIP extension first (make -C gym-os2r_amd/csrc). There is no CPU fallback.",
+                            "libos2r_control.so ABI version does not match gym_os2r_amd.control")
+    return _lib
 
 
 def slot_columns(task, nq):

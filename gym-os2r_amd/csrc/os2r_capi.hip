@@ -16,6 +16,7 @@
 #include <string>
 #include <vector>
 
+#include "os2r_host.hpp"
 #include "os2r_kernels.hpp"
 #include "os2r_lqr.hpp"
 #include "../../include/os2r_record.h"
@@ -96,19 +97,6 @@ static const JitEntry* find_jit(const Os2rModel& m, int dtype, int device, bool 
 namespace {
 
 thread_local std::string g_create_error;
-
-// Every entry point works on the device of its handle and leaves the caller's current device as it found it
-// (a process may hold handles on several GPUs; torch keeps its own idea of the current device).
-struct DeviceGuard {
-  int prev = -1, dev = -1;
-  explicit DeviceGuard(int device) : dev(device) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != dev) (void)hipSetDevice(dev);
-  }
-  ~DeviceGuard() {
-    if (prev >= 0 && prev != dev) (void)hipSetDevice(prev);
-  }
-};
 
 struct SimBase {
   Os2rConfig cfg;
@@ -256,16 +244,6 @@ void fill_task(const Os2rConfig& cfg, DevTask<T>& d) {
   d.dr_damping_lo = t.dr_damping_lo; d.dr_damping_hi = t.dr_damping_hi;
   d.dr_mu_base = t.dr_mu_base; d.dr_mu_lo = t.dr_mu_lo; d.dr_mu_hi = t.dr_mu_hi;
   for (int i = 0; i < OS2R_MAX_DOF; ++i) d.nominal_damping[i] = cfg.model.damping[i];
-}
-
-// The library is built with -fno-honor-nans -fno-honor-infinities: a comparison written to fail on a NaN, `!(x > 0.0)`, is compiled
-// as if there were none, and a NaN passes it (so does std::isfinite, and a test of the bits of a double passed by value: the
-// argument itself is declared free of NaNs).  The config's doubles are therefore tested on their bit pattern first, read from
-// memory as an integer.
-__attribute__((noinline)) bool is_finite(const double* x) {
-  uint64_t b;
-  std::memcpy(&b, x, sizeof(b));
-  return ((b >> 52) & 0x7ffu) != 0x7ffu;
 }
 
 int validate(const Os2rConfig* c, std::string& why) {
@@ -1008,15 +986,11 @@ int os2r_lqr_gains(Os2rSim* sim, int32_t nknots, int64_t ntraj, int32_t sweeps, 
   if (!q_host) { sim->err = "os2r_lqr_gains: null q_host"; return OS2R_ERR_INVALID; }
   if (!r_host) { sim->err = "os2r_lqr_gains: null r_host"; return OS2R_ERR_INVALID; }
   const int n = 2 * sim->nq;
-  // (bit patterns: the library is built without NaN semantics, see validate)
-  for (int i = 0; i < n * n; ++i)
-    if (!is_finite(&q_host[i])) { sim->err = "os2r_lqr_gains: Q must be finite"; return OS2R_ERR_INVALID; }
-  for (int i = 0; i < 4; ++i)
-    if (!is_finite(&r_host[i])) { sim->err = "os2r_lqr_gains: R must be finite"; return OS2R_ERR_INVALID; }
-  for (int i = 0; i < n; ++i)
-    for (int j = i + 1; j < n; ++j)
-      if (q_host[i * n + j] != q_host[j * n + i]) { sim->err = "os2r_lqr_gains: Q must be exactly symmetric"; return OS2R_ERR_INVALID; }
-  if (r_host[1] != r_host[2]) { sim->err = "os2r_lqr_gains: R must be exactly symmetric"; return OS2R_ERR_INVALID; }
+  // (bit patterns: the library is built without NaN semantics, see is_finite)
+  if (!all_finite(q_host, n * n)) { sim->err = "os2r_lqr_gains: Q must be finite"; return OS2R_ERR_INVALID; }
+  if (!all_finite(r_host, 4)) { sim->err = "os2r_lqr_gains: R must be finite"; return OS2R_ERR_INVALID; }
+  if (!symmetric(q_host, n)) { sim->err = "os2r_lqr_gains: Q must be exactly symmetric"; return OS2R_ERR_INVALID; }
+  if (!symmetric(r_host, 2)) { sim->err = "os2r_lqr_gains: R must be exactly symmetric"; return OS2R_ERR_INVALID; }
   if (!gain_dev && !p_out_dev && !weights_dev) { sim->err = "os2r_lqr_gains: all outputs are null (gain, p_out, weights)"; return OS2R_ERR_INVALID; }
   if (weights_dev && (!actions_dev || !obs_dev)) { sim->err = "os2r_lqr_gains: weights need actions_dev and obs_dev"; return OS2R_ERR_INVALID; }
   DeviceGuard guard(sim->cfg.device);

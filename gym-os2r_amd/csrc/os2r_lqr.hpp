@@ -26,6 +26,19 @@ namespace os2r {
 constexpr int kLqrEnvs = 32;                   // environments of one workgroup
 constexpr int kLqrMaxN = 2 * OS2R_MAX_DOF;
 
+// The chain length as a compile-time constant: f(std::integral_constant<int, NQ>()) for nq = NQ in 2..5 and 0, or 1 if there is
+// no kernel for this nq.  The launches of os2r_lqr_inst.hip, os2r_ilqr_inst.hip and os2r_search_inst.hip go through it.
+template <typename F>
+int by_chain_length(int nq, F&& f) {
+  switch (nq) {
+    case 2: f(std::integral_constant<int, 2>()); return 0;
+    case 3: f(std::integral_constant<int, 3>()); return 0;
+    case 4: f(std::integral_constant<int, 4>()); return 0;
+    case 5: f(std::integral_constant<int, 5>()); return 0;
+    default: return 1;
+  }
+}
+
 template <typename T>
 struct LqrArgs {
   const T* __restrict__ a;         // [n][n][L], L = nknots * ntraj, lane of (knot k, trajectory m) = k * ntraj + m

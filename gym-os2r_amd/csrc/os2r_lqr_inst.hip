@@ -10,21 +10,13 @@ namespace os2r {
 
 using T = OS2R_REAL;
 
-template <int NQ>
-static void launch_lqr(const LqrArgs<T>& p, hipStream_t s) {
-  const dim3 grid((unsigned)((p.M + kLqrEnvs - 1) / kLqrEnvs)), block(kLqrEnvs * (2 * NQ + 2));
-  hipLaunchKernelGGL((lqr_gains_kernel<T, NQ>), grid, block, 0, s, p);
-}
-
 template <>
 int launch_lqr_gains<T>(int nq, const LqrArgs<T>& p, hipStream_t s) {
-  switch (nq) {
-    case 2: launch_lqr<2>(p, s); return 0;
-    case 3: launch_lqr<3>(p, s); return 0;
-    case 4: launch_lqr<4>(p, s); return 0;
-    case 5: launch_lqr<5>(p, s); return 0;
-    default: return 1;
-  }
+  return by_chain_length(nq, [&](auto chain) {
+    constexpr int NQ = decltype(chain)::value;
+    const dim3 grid((unsigned)((p.M + kLqrEnvs - 1) / kLqrEnvs)), block(kLqrEnvs * (2 * NQ + 2));
+    hipLaunchKernelGGL((lqr_gains_kernel<T, NQ>), grid, block, 0, s, p);
+  });
 }
 
 }  // namespace os2r

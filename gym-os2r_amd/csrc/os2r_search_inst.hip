@@ -10,21 +10,13 @@ namespace os2r {
 
 using T = OS2R_REAL;
 
-template <int NQ>
-static void launch_search(const SearchArgs<T>& p, hipStream_t s) {
-  const dim3 grid((unsigned)((p.M + kSearchTraj - 1) / kSearchTraj)), block(kSearchTraj * p.nalpha);
-  hipLaunchKernelGGL((ilqr_line_search_kernel<T, NQ>), grid, block, 0, s, p);
-}
-
 template <>
 int launch_ilqr_line_search<T>(int nq, const SearchArgs<T>& p, hipStream_t s) {
-  switch (nq) {
-    case 2: launch_search<2>(p, s); return 0;
-    case 3: launch_search<3>(p, s); return 0;
-    case 4: launch_search<4>(p, s); return 0;
-    case 5: launch_search<5>(p, s); return 0;
-    default: return 1;
-  }
+  return by_chain_length(nq, [&](auto chain) {
+    constexpr int NQ = decltype(chain)::value;
+    const dim3 grid((unsigned)((p.M + kSearchTraj - 1) / kSearchTraj)), block(kSearchTraj * p.nalpha);
+    hipLaunchKernelGGL((ilqr_line_search_kernel<T, NQ>), grid, block, 0, s, p);
+  });
 }
 
 }  // namespace os2r

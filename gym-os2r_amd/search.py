@@ -11,6 +11,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 
+from ._lib import load_library
 from .control import MAX_ALPHAS, MAX_OBS, Os2rControlLayout, layout, slot_columns  # noqa: F401  (re-exported)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -39,18 +40,8 @@ class Os2rSearchLibraryMissing(ImportError):
 
 def load():
     global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise Os2rSearchLibraryMissing(
-            f"{LIB_PATH} not found: build the HIP extension first (make -C gym-os2r_amd/csrc). There is no CPU fallback.")
-    import torch  # noqa: F401  (first, so that the process holds one HIP runtime: gym_os2r_amd._lib.load says why)
-    lib = C.CDLL(LIB_PATH)
-    for name, argtypes in ENTRY_POINTS.items():
-        fn = getattr(lib, name)  # AttributeError here means header and library disagree
-        fn.argtypes = list(argtypes)
-        fn.restype = C.c_char_p if name == "os2rs_last_error" else C.c_int
-    if lib.os2rs_abi_version() != ABI_VERSION:
-        raise ImportError("libos2r_search.so ABI version does not match gym_os2r_amd.search")
-    _lib = lib
-    return lib
+    if _lib is None:
+        _lib = load_library(LIB_PATH, ENTRY_POINTS, "os2rs_last_error", ("os2rs_abi_version", ABI_VERSION), Os2rSearchLibraryMissing,
+                            "build the HIP extension first (make -C gym-os2r_amd/csrc). There is no CPU fallback.",
+                            "libos2r_search.so ABI version does not match gym_os2r_amd.search")
+    return _lib

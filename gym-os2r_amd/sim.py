@@ -58,6 +58,15 @@ class HipSim:
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
+    def _layout(self):
+        """The handle as the companion libraries take it (an Os2rControlLayout), filled once from the handle's config."""
+        lay = self.__dict__.get("_control_layout")
+        if lay is None:
+            from . import control
+            lay = self._control_layout = control.layout(abi.F64 if self.dtype == torch.float64 else abi.F32, self.nq, self.cfg.device,
+                                                        control.slot_columns(self.cfg.task, self.nq))
+        return lay
+
     def _new(self, *shape, dtype=None):
         return torch.empty(*shape, dtype=dtype or self.dtype, device=self.device)
 
@@ -761,10 +770,7 @@ class HipSim:
             actions = obs = None
         from . import control
         lib = control.load()
-        lay = self.__dict__.get("_control_layout")
-        if lay is None:       # filled once from the handle's config
-            lay = self._control_layout = control.layout(abi.F64 if self.dtype == torch.float64 else abi.F32, self.nq, self.cfg.device,
-                                                        control.slot_columns(self.cfg.task, self.nq))
+        lay = self._layout()
         rc = lib.os2rc_ilqr_backward(C.byref(lay), K, M, _ptr(A), _ptr(B), _ptr(lx), _ptr(lu), q, r, mu, _ptr(P_final), _ptr(p_final),
                                      _ptr(gains_out), _ptr(ff_out), _ptr(P_out), _ptr(p_out), _ptr(flags_out), _ptr(dv_out), _ptr(actions),
                                      _ptr(obs), al, nal, _ptr(weights_out), self._stream())
@@ -881,12 +887,9 @@ class HipSim:
         self._out(index, (L,), torch.int32, f"{what}: index")
         if end_obs is None or actions is None:
             raise ValueError(f"{what}: end_obs and actions are required")
-        from . import control, search
+        from . import search
         lib = search.load()
-        lay = self.__dict__.get("_control_layout")
-        if lay is None:       # filled once from the handle's config (shared with ilqr_backward)
-            lay = self._control_layout = control.layout(abi.F64 if self.dtype == torch.float64 else abi.F32, self.nq, self.cfg.device,
-                                                        control.slot_columns(self.cfg.task, self.nq))
+        lay = self._layout()
         rc = lib.os2rs_ilqr_line_search(C.byref(lay), K, M, nal, search.ACCEPT_ALWAYS if always else 0, _ptr(knot_obs), _ptr(end_obs),
                                         _ptr(actions), _ptr(done), _ptr(target), q, r, qf, _ptr(cost), _ptr(act_nom), _ptr(obs_nom),
                                         _ptr(end_nom), _ptr(lx), _ptr(lu), _ptr(p_final), _ptr(choice), _ptr(index), _ptr(cand_cost),

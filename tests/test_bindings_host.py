@@ -5,43 +5,15 @@ looks for a device.  No GPU needed."""
 import ctypes as C
 import importlib
 import inspect
-import os
 import re
 
 import pytest
 
-from conftest import ROOT
 from gym_os2r_amd import _lib, abi
-
-INTEGERS = {"int": (C.c_int, C.c_int32), "int32_t": (C.c_int, C.c_int32), "int64_t": (C.c_int64,), "uint32_t": (C.c_uint32,),
-            "uint64_t": (C.c_uint64,)}
-
-
-def _is_pointer(ctype):
-    return ctype in (C.c_void_p, C.c_char_p) or issubclass(ctype, C._Pointer)
-
-
-def _prototypes():
-    """-> [(name, result type text, [argument text, ...])] in the header's order."""
-    with open(os.path.join(ROOT, "include", "os2r.h")) as f:
-        header = re.sub(r"/\*.*?\*/", " ", f.read(), flags=re.S)
-    out = []
-    for ret, name, args in re.findall(r"OS2R_API\s+([^;()]*?)\s*\b(os2r_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", header, re.S):
-        args = [" ".join(a.split()) for a in args.split(",")]
-        out.append((name, " ".join(ret.split()), [] if args == ["void"] else args))
-    return out
-
-
-def _agrees(c_text, ctype, with_name):
-    """One parameter (`with_name`) or result type of the header against its ctypes type, class by class."""
-    if "*" in c_text or "[" in c_text:
-        return _is_pointer(ctype)
-    base = c_text.split()[:-1] if with_name else c_text.split()
-    return len(base) == 1 and ctype in INTEGERS.get(base[0], ())
-
+from header_check import _agrees, _is_pointer, _prototypes
 
 def test_the_table_is_the_header():
-    protos = _prototypes()
+    protos = _prototypes("os2r.h", "os2r")
     assert len(protos) == 35
     assert [p[0] for p in protos] == list(_lib.ENTRY_POINTS) == _lib.SYMBOLS
     lib = _lib.load()

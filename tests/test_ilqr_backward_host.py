@@ -16,39 +16,15 @@ from conftest import ROOT
 from gym_os2r_amd import abi
 
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+from header_check import _agrees, _is_pointer, _prototypes, checks_before_the_device, the_finite_and_symmetric_tests_make_no_hip_call  # noqa: E402
 
-INTEGERS = {"int": (C.c_int, C.c_int32), "int32_t": (C.c_int, C.c_int32), "int64_t": (C.c_int64,)}
 CASES = ((10, 4, 70), (4, 3, 3), (6, 2, 33), (8, 2, 33))
 
-
-def _is_pointer(ctype):
-    return ctype in (C.c_void_p, C.c_char_p) or issubclass(ctype, C._Pointer)
-
-
-def _prototypes():
-    """-> [(name, result type text, [argument text, ...])] in the header's order."""
-    with open(os.path.join(ROOT, "include", "os2r_control.h")) as f:
-        header = re.sub(r"/\*.*?\*/", " ", f.read(), flags=re.S)
-    out = []
-    for ret, name, args in re.findall(r"OS2R_API\s+([^;()]*?)\s*\b(os2rc_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", header, re.S):
-        args = [" ".join(a.split()) for a in args.split(",")]
-        out.append((name, " ".join(ret.split()), [] if args == ["void"] else args))
-    return out
-
-
-def _agrees(c_text, ctype, with_name):
-    """One parameter (`with_name`) or result type of the header against its ctypes type, class by class."""
-    if "*" in c_text or "[" in c_text:
-        return _is_pointer(ctype)
-    base = c_text.split()[:-1] if with_name else c_text.split()
-    if base == ["double"]:
-        return ctype is C.c_double                                   # by value
-    return len(base) == 1 and ctype in INTEGERS.get(base[0], ())
 
 
 def test_the_table_is_the_header_and_the_library_exports_it():
     from gym_os2r_amd import control
-    protos = _prototypes()
+    protos = _prototypes("os2r_control.h", "os2rc")
     assert [p[0] for p in protos] == list(control.ENTRY_POINTS) == ["os2rc_abi_version", "os2rc_last_error", "os2rc_ilqr_backward"]
     lib = control.load()
     for name, ret, args in protos:
@@ -162,13 +138,9 @@ def test_refusals_come_through_ctypes_without_a_device():
         seen.add(err)
     assert len(seen) == len({m for _, m in cases}) == 22            # each cause has a text of its own
     assert not any(buf)                                             # a refused call wrote nothing
-    with open(os.path.join(ROOT, "gym-os2r_amd", "csrc", "os2r_control_capi.hip")) as f:
-        src = f.read()
-    body = re.search(r"int os2rc_ilqr_backward\(.*?\n}\n", src, re.S).group(0)
-    first_hip = min(body.index(t) for t in ("check_device(", "DeviceGuard", "launch<"))
-    assert not re.search(r"\bhip[A-Z]\w*\(", body[:first_hip])      # no HIP call of its own before that point
-    assert all(body.index(m) < first_hip for m in re.findall(r'fail\(OS2R_ERR_INVALID, "([^"]+)"', body))
-    assert len(re.findall(r"fail\(OS2R_ERR_INVALID", body)) == 22
+    texts = checks_before_the_device("os2r_control_capi.hip", "os2rc_ilqr_backward", ("layout_refusal", "slots_refusal"))
+    assert len(texts) == 22
+    the_finite_and_symmetric_tests_make_no_hip_call()
 
 
 def test_kernel_resources():

@@ -17,44 +17,16 @@ from conftest import ROOT
 from gym_os2r_amd import abi
 
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+from header_check import _agrees, _header, _is_pointer, _prototypes, checks_before_the_device, the_finite_and_symmetric_tests_make_no_hip_call  # noqa: E402
 
-INTEGERS = {"int": (C.c_int, C.c_int32), "int32_t": (C.c_int, C.c_int32), "int64_t": (C.c_int64,), "uint32_t": (C.c_uint32, C.c_uint)}
 NAMES = ["os2rs_abi_version", "os2rs_last_error", "os2rs_ilqr_line_search"]
 CONTROL_KERNELS = 8
 
 
-def _is_pointer(ctype):
-    return ctype in (C.c_void_p, C.c_char_p) or issubclass(ctype, C._Pointer)
-
-
-def _header(name="os2r_search.h"):
-    with open(os.path.join(ROOT, "include", name)) as f:
-        return f.read()
-
-
-def _prototypes():
-    """-> [(name, result type text, [argument text, ...])] in the header's order."""
-    header = re.sub(r"/\*.*?\*/", " ", _header(), flags=re.S)
-    out = []
-    for ret, name, args in re.findall(r"OS2R_API\s+([^;()]*?)\s*\b(os2rs_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", header, re.S):
-        args = [" ".join(a.split()) for a in args.split(",")]
-        out.append((name, " ".join(ret.split()), [] if args == ["void"] else args))
-    return out
-
-
-def _agrees(c_text, ctype, with_name):
-    """One parameter (`with_name`) or result type of the header against its ctypes type, class by class."""
-    if "*" in c_text or "[" in c_text:
-        return _is_pointer(ctype)
-    base = c_text.split()[:-1] if with_name else c_text.split()
-    if base == ["double"]:
-        return ctype is C.c_double
-    return len(base) == 1 and ctype in INTEGERS.get(base[0], ())
-
 
 def test_the_table_is_the_header_and_the_library_exports_it():
     from gym_os2r_amd import control, search
-    protos = _prototypes()
+    protos = _prototypes("os2r_search.h", "os2rs")
     assert [p[0] for p in protos] == list(search.ENTRY_POINTS) == NAMES
     lib = search.load()
     for name, ret, args in protos:
@@ -69,7 +41,7 @@ def test_the_table_is_the_header_and_the_library_exports_it():
     args = protos[2][2]
     assert len(args) == 24 and args[:5] == ["const Os2rControlLayout* layout", "int32_t nknots", "int64_t ntraj", "int32_t nalpha", "uint32_t flags"]
     assert args[-1] == "void* stream" and search.ENTRY_POINTS["os2rs_ilqr_line_search"][4] is C.c_uint32
-    header = _header()
+    header = _header("os2r_search.h")
     assert re.search(r"#define OS2R_SEARCH_ABI_VERSION 1\b", header) and re.search(r"#define OS2RS_ACCEPT_ALWAYS 1u\b", header)
     assert '#include "os2r_control.h"' in header and "typedef struct" not in header      # the layout is os2r_control.h's
     assert lib.os2rs_abi_version() == search.ABI_VERSION == 1 and search.ACCEPT_ALWAYS == 1
@@ -158,16 +130,9 @@ def test_refusals_come_through_ctypes_without_a_device():
     assert not any(buf)                                             # a refused call wrote nothing
     # 2^31 - 1 lanes themselves are taken by the checks (the next refusal is about something else)
     assert call(K=1, M=2 ** 31 - 1, nal=1, q=None) == abi.ERR_INVALID and lib.os2rs_last_error().endswith(b"null q_host")
-    with open(os.path.join(ROOT, "gym-os2r_amd", "csrc", "os2r_search_capi.hip")) as f:
-        src = f.read()
-    body = re.search(r"int os2rs_ilqr_line_search\(.*?\n}\n", src, re.S).group(0)
-    first_hip = min(body.index(t) for t in ("check_device(", "DeviceGuard", "launch<"))
-    assert not re.search(r"\bhip[A-Z]\w*\(", body[:first_hip])      # no HIP call of its own before that point
-    assert all(body.index(m) < first_hip for m in re.findall(r'fail\(OS2R_ERR_INVALID, "([^"]+)"', body))
-    assert len(re.findall(r"fail\(OS2R_ERR_INVALID", body)) == 24
-    for helper in ("is_finite", "all_finite", "symmetric"):       # and the helpers the checks call make none either
-        text = re.search(r"bool " + helper + r"\(.*?\n}\n", src, re.S).group(0)
-        assert not re.search(r"\bhip[A-Z]\w*\(", text), helper
+    texts = checks_before_the_device("os2r_search_capi.hip", "os2rs_ilqr_line_search", ("layout_refusal", "slots_refusal"))
+    assert len(texts) == 24
+    the_finite_and_symmetric_tests_make_no_hip_call()
 
 
 def test_kernel_resources():
@@ -209,7 +174,7 @@ def test_the_restatement_follows_the_header_and_agrees_with_the_direct_formula()
     printed."""
     import inspect
     import test_gpu_ilqr_line_search as t
-    header = " ".join(_header().replace("\n *", " ").split())
+    header = " ".join(_header("os2r_search.h").replace("\n *", " ").split())
     at = [header.find(s) for s in STEPS]
     assert all(a >= 0 for a in at) and at == sorted(at), at
     src = inspect.getsource(t.restate)

@@ -77,8 +77,11 @@ def test_refusals_come_before_the_device_is_touched():
                 "null r_host", "Q must be finite", "R must be finite", "Q must be exactly symmetric", "R must be exactly symmetric",
                 "all outputs are null", "weights need actions_dev and obs_dev"):
         assert msg in body, msg
-    assert body.index("is_finite(&q_host[i])") < body.index("q_host[i * n + j] != q_host[j * n + i]") < body.index("DeviceGuard")
-    assert body.index("is_finite(&r_host[i])") < body.index("r_host[1] != r_host[2]") < body.index("DeviceGuard")
+    assert body.index("!all_finite(q_host, n * n)") < body.index("!symmetric(q_host, n)") < body.index("DeviceGuard")
+    assert body.index("!all_finite(r_host, 4)") < body.index("!symmetric(r_host, 2)") < body.index("DeviceGuard")
+    assert not re.search(r"\bhip[A-Z]\w*\(", body[:body.index("DeviceGuard")])
+    from header_check import the_finite_and_symmetric_tests_make_no_hip_call
+    the_finite_and_symmetric_tests_make_no_hip_call()      # (and they read bit patterns and compare exactly)
 
 
 def test_lqr_kernel_resources():
