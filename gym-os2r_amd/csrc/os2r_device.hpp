@@ -1351,7 +1351,7 @@ __device__ __forceinline__ void substep(const MD& md, const Params<T, MD, DR>& p
   };
   // ---- exact finish (fp64; kExact* above).  The rows of phase 2 in sweep order: ----
   // f(slot, nz, g, target, rd, lambda&, lo, hi, upper): row `slot` has the non-zeros g[0..nz], the reciprocal rd of its squared norm
-  // and an impulse in [lo, hi] (upper == false: no upper bound)
+  // and an impulse in [lo, hi] (upper == false: no upper bound; upper == true: lo == -hi, which the exact solve's free test uses)
   auto each_row = [&](auto first, auto&& f) {
     constexpr int kFirst = decltype(first)::value;
 #pragma unroll
@@ -1397,7 +1397,9 @@ __device__ __forceinline__ void substep(const MD& md, const Params<T, MD, DR>& p
     // Branch-free on purpose (bitwise logic on the predicates, selects, min / max): written with && / || and
     // conditional statements every row became a divergent branch of its own -- a hundred of them per solve, each a
     // handful of scalar instructions on the execution mask plus the jump, which a lone wave pays in full.
-    auto is_free = [](T l, T lo, T hi, bool upper) { return (l > lo) & (upper ? (l < hi) : true); };
+    // (every row with an upper bound has the box [-hi, hi] -- friction rows --, so "strictly inside" is ONE compare of |l|: the
+    // same verdict for every value, the zero-width box and NaN included, for one v_cmp instead of two and a scalar and)
+    auto is_free = [](T l, T lo, T hi, bool upper) { return upper ? (fabs_t(l) < hi) : (l > lo); };
     T S[NT], h[NQ];
 #pragma unroll
     for (int k = 0; k < NT; ++k) S[k] = T(0);
@@ -1423,8 +1425,8 @@ __device__ __forceinline__ void substep(const MD& md, const Params<T, MD, DR>& p
       // (a body that none of the lanes at work touches has its rows switched off in all of them -- impulse 0 in a box [0, 0], never
       // free --: three votes less per such body, typically one of the three a wave carries when a lone lane is in a burst)
       if (slot < 3 * NB && (touch[slot / 3] & at_work) == 0ull) return;
-      // (a ballot per comparison: the ballot of their conjunction is lowered through a 0 / 1 register and a second compare)
-      const unsigned long long fm = __builtin_amdgcn_ballot_w64(l > lo) & (upper ? __builtin_amdgcn_ballot_w64(l < hi) : ~0ull);
+      // (the ballot of one comparison: that of a conjunction is lowered through a 0 / 1 register and a second compare)
+      const unsigned long long fm = upper ? __builtin_amdgcn_ballot_w64(fabs_t(l) < hi) : __builtin_amdgcn_ballot_w64(l > lo);
       U |= fm != 0ull ? (1u << slot) : 0u;
     });
     // pass 1: S = sum over the free rows of g g^T, h = -sum g w, w = g.y - target
@@ -1525,7 +1527,9 @@ __device__ __forceinline__ void substep(const MD& md, const Params<T, MD, DR>& p
     auto pass2 = [&](auto measure_) {
       each_row_in(first, U, [&](int slot, int nz, const T (&g)[NQ], T target, T rd, T& l, T lo, T hi, bool upper) {
         const bool fr = is_free(l, lo, hi, upper);
-        const T f = opaque(fr ? opaque(ieps * rd) : T(0));
+        // (the product outside the select: inside it, the pinned product became a divergent branch around one v_mul)
+        const T ir = opaque(ieps * rd);
+        const T f = opaque(fr ? ir : T(0));
         T w = -target;
 #pragma unroll
         for (int k = 0; k < NQ; ++k)
