@@ -3,7 +3,7 @@
 by side towards a target posture, the backward pass in one os2rc_ilqr_backward launch.
 
   python examples/ilqr_balancing.py [--envs 64] [--steps 40] [--iters 10] [--settle 300] [--perturb 0.05] [--mu 0.0] [--eps 1e-4]
-                                    [--knots recorded|loop] [--line-search torch|device]
+                                    [--knots recorded|loop] [--line-search torch|device|steered] [--armijo 0] [--tol 0] [--poll P]
 
 The cost of a trajectory is sum_k 1/2 (x_k - x*)'Q(x_k - x*) + 1/2 a_k'R a_k plus 1/2 (x_K - x*)'Q(x_K - x*), read off the raw
 observation slots (state components the task does not observe carry no weight); x* is the posture the PD of lqr_balancing.py
@@ -34,6 +34,16 @@ reshuffled in between; the host reads back one flag, (choice >= 0).any(), to ste
 anything), and for its printed line the mean cost and how many trajectories took which step size.  The first nominal is
 initialised by the same call with one candidate per trajectory.  The default, --line-search torch, is the iteration above with
 one step size for the whole batch.
+With --line-search steered (needs --knots recorded) mu is one number per trajectory and lives on the device: the backward pass
+reads it there (ilqr_backward(mu_dev=...): os2rt_ilqr_backward_mu), and the line search is os2rt_ilqr_steer (HipSim.ilqr_steer),
+which in its one launch also halves the mu of every trajectory that accepted a step, raises the mu of every trajectory that did
+not -- the rule above, per trajectory --, applies an Armijo test on the predicted change (--armijo c: a step must lower the
+cost by at least c times what the model predicts; 0: none) and freezes a trajectory whose accepted step lowered its cost by no
+more than --tol times its cost (converged) or whose mu would pass 1e6 (stalled).  The iteration is linearize, ilqr_backward,
+copy_envs_from, rollout_schedule, ilqr_steer, copy_envs_from, with nothing read back inside the loop: the host launches the
+iterations back to back and every --poll P iterations (default: only after the last) reads status, mu, iters and the costs
+once, and prints the mean cost, the histogram of mu and how many trajectories are active, converged and stalled.  Frozen
+trajectories still run through the backward pass and the rollout; they are just never accepted.
 Printed per iteration: the cost (mean over the trajectories), the step size, mu, the refused knots, and the predicted against
 the actual change.  The script prints what happened; it claims no control quality: a quotient across a change of contact mode
 is a secant, the default eps is not tuned, and the actions saturate, which the model knows nothing about.
@@ -67,14 +77,18 @@ def main():
     ap.add_argument("--knots", choices=("recorded", "loop"), default="recorded",
                     help="recorded: the candidates' rollout records the knots (five launches per iteration); loop: the nominal is "
                          "replayed and forked knot by knot")
-    ap.add_argument("--line-search", choices=("torch", "device"), default="torch",
+    ap.add_argument("--line-search", choices=("torch", "device", "steered"), default="torch",
                     help="torch: costs and one step size for the whole batch in torch; device: one os2rs_ilqr_line_search launch, a step "
-                         "size per trajectory (needs --knots recorded)")
+                         "size per trajectory (needs --knots recorded); steered: one os2rt_ilqr_steer launch, which also keeps a mu per "
+                         "trajectory on the device (needs --knots recorded)")
+    ap.add_argument("--armijo", type=float, default=0.0, help="steered: a step must lower the cost by this times the predicted change")
+    ap.add_argument("--tol", type=float, default=0.0, help="steered: a trajectory converges when a step lowers its cost by no more than tol |cost|")
+    ap.add_argument("--poll", type=int, default=0, help="steered: read the device every P iterations (0: only after the last)")
     args = ap.parse_args()
     M, K, nal = args.envs, args.steps, len(ALPHAS)
     recorded = args.knots == "recorded"
-    if args.line_search == "device" and not recorded:
-        ap.error("--line-search device needs --knots recorded")
+    if args.line_search in ("device", "steered") and not recorded:
+        ap.error(f"--line-search {args.line_search} needs --knots recorded")
     # one task, three handles: the nominal (M trajectories), the knots (K M lanes, knot-major), the candidates (4 M environments);
     # recorded: a fourth for the knots of every candidate (K 4 M lanes, knot-major)
     envs = [g.make("Monopod-nonorm-balance-v1", num_envs=n, seed=args.seed) for n in (M, K * M, nal * M) + ((K * nal * M,) if recorded else ())]
@@ -122,8 +136,9 @@ def main():
     first = torch.arange(M, dtype=torch.int32, device=dev).repeat(nal)                # knot 0 of trajectory m, once per step size
     U = torch.zeros(K, M, 2, dtype=dt, device=dev)
     mu, it, tries, shown_cost = args.mu, 0, 0, None
-    if args.line_search == "device":
-        line_search_on_device(args, nom, knots, cand, cand_knots, start, target_obs, Q.cpu(), R.cpu(), first)
+    if args.line_search in ("device", "steered"):
+        loop = line_search_on_device if args.line_search == "device" else steered_on_device
+        loop(args, nom, knots, cand, cand_knots, start, target_obs, Q.cpu(), R.cpu(), first)
         for e in envs:
             e.close()
         return
@@ -251,6 +266,44 @@ def line_search_on_device(args, nom, knots, cand, cand_knots, start, target, Q, 
     while it < args.iters:                                                            # (kept: every iteration has its line)
         it += 1
         print(f"iter {it:2d} cost {float(nominal['cost'].mean()):.6e} (no step size was accepted)", flush=True)
+
+
+def steered_on_device(args, nom, knots, cand, cand_knots, start, target, Q, R, first):
+    """The iteration with HipSim.ilqr_steer and a mu per trajectory on the device: linearize, ilqr_backward(mu_dev=...),
+    copy_envs_from (knot 0 -> candidates), rollout_schedule (recorded), ilqr_steer, copy_envs_from (the accepted knots); the host
+    reads nothing inside the loop."""
+    M, K, nal = args.envs, args.steps, len(ALPHAS)
+    dev, dt, D = nom.device, nom.dtype, nom.D
+    table0 = torch.zeros(M, K, 2, D + 1, dtype=dt, device=dev)
+    nom.restore(start)
+    _, _, (o_n, _, d_n, _, _), (a_n, _), kobs = nom.rollout_schedule(K, table0, want_outputs=True, want_actions=True, knots=knots,
+                                                                     want_knot_obs=True)
+    choice, _, _, nominal = nom.ilqr_line_search(kobs, o_n[K - 1], a_n, target, Q, R, done=d_n, want_cand_cost=False)
+    nominal["mu"] = torch.full((M,), args.mu, dtype=dt, device=dev)
+    print(f"iter {0:2d} cost {float(nominal['cost'].mean()):.6e} (the nominal: zero torque; {int((choice < 0).sum())} of {M} trajectories "
+          f"had an episode end inside it and stay out)", flush=True)
+    a_k, obs_k = nominal["actions"].view(K * M, 2), nominal["obs"].view(K * M, D)        # views: updated in place by every call
+    edges = (0.0, 1e-3, 1e-1, 1e1, 1e3)
+    for it in range(1, args.iters + 1):
+        _, _, A, B = knots.linearize(a_k, args.eps, want_next=False)
+        _, _, _, _, _, dv, table = nom.ilqr_backward(A, B, Q, R, knots=K, lx=nominal["lx_view"], lu=nominal["lu_view"], mu_dev=nominal["mu"],
+                                                     p_final=nominal["p_final_view"], actions=a_k, obs=obs_k, alphas=ALPHAS,
+                                                     want_gains=False, want_ff=False, want_flags=False, want_weights=True)
+        cand.copy_envs_from(knots, first)
+        _, _, (o_c, _, d_c, _, _), (a_c, _), kobs_c = cand.rollout_schedule(K, table, want_outputs=True, want_actions=True,
+                                                                          knots=cand_knots, want_knot_obs=True)
+        _, index, _, _ = nom.ilqr_steer(kobs_c, o_c[K - 1], a_c, target, Q, R, dv, ALPHAS, nominal=nominal, done=d_c, want_cand_cost=False,
+                                        armijo=args.armijo, tol=args.tol)
+        knots.copy_envs_from(cand_knots, index)
+        if it == args.iters or (args.poll > 0 and it % args.poll == 0):
+            # the poll: one look at the device
+            cost, mu, status, iters = (nominal[k].cpu() for k in ("cost", "mu", "status", "iters"))
+            hist = [int((mu == 0).sum())] + [int(((mu > lo) & (mu <= hi)).sum()) for lo, hi in zip(edges, edges[1:])] + [int((mu > edges[-1]).sum())]
+            names = ["0"] + [f"<={hi:g}" for hi in edges[1:]] + [f">{edges[-1]:g}"]
+            state = torch.bincount(status, minlength=3).tolist()
+            print(f"iter {it:2d} cost {float(cost.mean()):.6e} mu " + ", ".join(f"{c} x {nm}" for c, nm in zip(hist, names)) +
+                  f"; active {state[0]} converged {state[1]} stalled {state[2]}; accepted steps per trajectory {int(iters.min())}.."
+                  f"{int(iters.max())}", flush=True)
 
 
 if __name__ == "__main__":

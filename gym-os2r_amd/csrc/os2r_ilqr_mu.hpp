@@ -1,0 +1,255 @@
+// os2r_ilqr_mu.hpp — os2rt_ilqr_backward_mu: the backward pass of iLQR with one regularisation mu per trajectory (gfx950).
+//
+// The kernel is ilqr_backward_kernel of os2r_ilqr.hpp -- the same lane layout (32 trajectories x (n + 2) columns, P, A, B, G, K
+// in LDS), the same phases, the same operations in the same order -- with two differences:
+//   mu       every lane loads its trajectory's mu once, into a register; where the kernel of os2r_ilqr.hpp branches on the
+//            argument mu != 0 (T = S + mu, the last terms of steps 7 and 8), this one selects per lane: a lane whose mu is 0
+//            keeps S, P' and p' as they are and never adds a zero, so every trajectory gets the bits os2rc_ilqr_backward gives
+//            it when called with its mu.  A mu that is negative or not finite (on its bit pattern: the host cannot look) runs
+//            as 0 with every knot of the trajectory refused.
+//   barrier  the one between phases 2a and 2b is always taken: it must be uniform over the workgroup, and neighbouring
+//            trajectories differ in whether they need the K of the other columns.
+// No lane indexes a register array at run time, nothing goes to scratch (tests/test_ilqr_steer_host.py reads the metadata).
+//
+// The arithmetic is the contract of include/os2r_control.h, steps 1-10, with mu read per trajectory (include/os2r_steer.h).
+#pragma once
+#include "os2r_ilqr.hpp"
+#include "../../include/os2r_steer.h"
+
+namespace os2r {
+
+// The bits of a value, through an empty asm on the INTEGER: what comes out has no floating-point history, so the class tests below
+// are compiled as written.  (The libraries are built without NaN / infinity semantics; a bit test of a float that passed
+// through an asm as a float -- lqr_finite -- is still recognised as a class test of that float and folded away: DESIGN.md
+// section 4 has what the assembly holds in its place.)
+__device__ __forceinline__ unsigned steer_bits(float x) {
+  unsigned b = (unsigned)__float_as_int(x);
+  asm volatile("" : "+v"(b));
+  return b;
+}
+__device__ __forceinline__ unsigned long long steer_bits(double x) {
+  unsigned long long b = (unsigned long long)__double_as_longlong(x);
+  asm volatile("" : "+v"(b));
+  return b;
+}
+__device__ __forceinline__ bool steer_finite(float x) { return (steer_bits(x) >> 23 & 0xffu) != 0xffu; }
+__device__ __forceinline__ bool steer_finite(double x) { return (steer_bits(x) >> 52 & 0x7ffull) != 0x7ffull; }
+__device__ __forceinline__ bool steer_nan(float x) { return (steer_bits(x) & 0x7fffffffu) > 0x7f800000u; }
+__device__ __forceinline__ bool steer_nan(double x) { return (steer_bits(x) & 0x7fffffffffffffffull) > 0x7ff0000000000000ull; }
+// negative, or not finite: by the sign bit of a value that is no zero
+__device__ __forceinline__ bool steer_invalid(float x) {
+  const unsigned b = steer_bits(x);
+  return (b >> 23 & 0xffu) == 0xffu || (b >> 31 != 0u && (b & 0x7fffffffu) != 0u);
+}
+__device__ __forceinline__ bool steer_invalid(double x) {
+  const unsigned long long b = steer_bits(x);
+  return (b >> 52 & 0x7ffull) == 0x7ffull || (b >> 63 != 0ull && (b & 0x7fffffffffffffffull) != 0ull);
+}
+
+template <typename T>
+struct IlqrMuArgs {
+  IlqrArgs<T> base;                // as os2rc_ilqr_backward fills it; base.mu is not read
+  const T* __restrict__ mu;        // [M]
+};
+
+template <typename T, int NQ>
+__global__ __launch_bounds__(kLqrEnvs * (2 * NQ + 2)) void ilqr_backward_mu_kernel(const IlqrMuArgs<T> PM) {
+#pragma clang fp contract(off)
+  constexpr int n = 2 * NQ, E = kLqrEnvs;
+  const IlqrArgs<T>& P = PM.base;
+  __shared__ T sP[n * n * E], sA[n * n * E], sB[n * 2 * E], sG[2 * (n + 2) * E], sK[2 * n * E], sQ[n * n];
+  __shared__ T sp[n * E], sQu[2 * E], sKf[2 * E], sAl[OS2RC_MAX_ALPHAS];
+  const int e = threadIdx.x % E, c = threadIdx.x / E;   // c is uniform over a half-wave, c < n over a wave (n is even)
+  const bool col_lane = c < n;
+  const long long M = P.M, m_raw = (long long)blockIdx.x * E + e;
+  const bool valid = m_raw < M;
+  const long long m = valid ? m_raw : M - 1;            // tail lanes shadow the last trajectory, their stores are masked
+  const int K = P.K;
+  const long long L = (long long)K * M;
+  // the lane's column of [A | B]: element l at src[l * stride + k * M]; its entry of [lx | lu] at grad[k * M]
+  const T* src = col_lane ? P.a + (long long)c * L + m : P.b + (long long)(c - n) * L + m;
+  const long long stride = (col_lane ? n : 2) * L;
+  const T* gbase = col_lane ? P.lx : P.lu;
+  const T* grad = gbase ? gbase + (long long)(col_lane ? c : c - n) * L + m : nullptr;
+  // the trajectory's mu, once: negative or not finite runs as 0 with every knot refused
+  const T mu_in = PM.mu[m];
+  const bool mu_bad = steer_invalid(mu_in);
+  const T mu = mu_bad ? T(0) : mu_in;
+  const bool reg = mu != T(0);
+
+  {  // Q and the step sizes for everybody (read with a lane index: from the argument segment as memory, not from a copy of the struct)
+    const OS2R_CONST IlqrMuArgs<T>* ka = (const OS2R_CONST IlqrMuArgs<T>*)__builtin_amdgcn_kernarg_segment_ptr();
+    if ((int)threadIdx.x < n * n) sQ[threadIdx.x] = ka->base.q[threadIdx.x];
+    if ((int)threadIdx.x < OS2RC_MAX_ALPHAS) sAl[threadIdx.x] = ka->base.alpha[threadIdx.x];
+  }
+  __syncthreads();
+  if (col_lane) {
+#pragma unroll
+    for (int i = 0; i < n; ++i)
+      if (i <= c) {
+        const T p = P.pmat_final ? P.pmat_final[(long long)(i * n + c) * M + m] : sQ[i * n + c];
+        sP[(i * n + c) * E + e] = p;
+        sP[(c * n + i) * E + e] = p;
+      }
+    sp[c * E + e] = P.pvec_final ? P.pvec_final[(long long)c * M + m] : T(0);
+  }
+
+  int k = K - 1;
+  T v[n], vn[n];
+#pragma unroll
+  for (int l = 0; l < n; ++l) vn[l] = v[l] = src[l * stride + (long long)k * M];
+  T gr = grad ? grad[(long long)k * M] : T(0), grn = gr;
+
+  for (; k >= 0; --k) {
+    if (!col_lane) {
+#pragma unroll
+      for (int l = 0; l < n; ++l) sB[(l * 2 + (c - n)) * E + e] = v[l];
+    }
+    __syncthreads();
+    // the next knot's column and gradient entry, in flight during this knot
+    if (k > 0) {
+#pragma unroll
+      for (int l = 0; l < n; ++l) vn[l] = src[l * stride + (long long)(k - 1) * M];
+      if (grad) grn = grad[(long long)(k - 1) * M];
+    }
+    // phase 1
+    T pv[n];
+#pragma unroll
+    for (int i = 0; i < n; ++i) {
+      T acc = sP[(i * n + 0) * E + e] * v[0];
+#pragma unroll
+      for (int l = 1; l < n; ++l) acc = acc + sP[(i * n + l) * E + e] * v[l];
+      pv[i] = acc;
+    }
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      T acc = sB[(0 * 2 + r) * E + e] * pv[0];
+#pragma unroll
+      for (int l = 1; l < n; ++l) acc = acc + sB[(l * 2 + r) * E + e] * pv[l];
+      sG[(r * (n + 2) + c) * E + e] = acc;
+    }
+    T gv;   // Qx[c] of a column lane, Qu[b] of an input lane
+    {
+      T acc = v[0] * sp[0 * E + e];
+#pragma unroll
+      for (int l = 1; l < n; ++l) acc = acc + v[l] * sp[l * E + e];
+      gv = gr + acc;
+    }
+    if (col_lane) {
+#pragma unroll
+      for (int l = 0; l < n; ++l) sA[(l * n + c) * E + e] = v[l];
+    } else {
+      sQu[(c - n) * E + e] = gv;
+    }
+    __syncthreads();
+    // phase 2a
+    T k0 = T(0), k1 = T(0), f0 = T(0), f1 = T(0);
+    if (col_lane) {
+      const T s00 = P.r00 + sG[(0 * (n + 2) + n) * E + e];
+      const T s01 = P.r01 + sG[(0 * (n + 2) + n + 1) * E + e];
+      const T s11 = P.r11 + sG[(1 * (n + 2) + n + 1) * E + e];
+      const T t00 = reg ? s00 + mu : s00, t11 = reg ? s11 + mu : s11;
+      const T det = t00 * t11 - s01 * s01;
+      const bool ok = lqr_finite(det) && t00 > T(0) && det > T(0) && !mu_bad;
+      const T g0 = sG[(0 * (n + 2) + c) * E + e], g1 = sG[(1 * (n + 2) + c) * E + e];
+      const T qu0 = sQu[0 * E + e], qu1 = sQu[1 * E + e];
+      k0 = (t11 * g0 - s01 * g1) / det;
+      k1 = (t00 * g1 - s01 * g0) / det;
+      f0 = lqr_neg((t11 * qu0 - s01 * qu1) / det);
+      f1 = lqr_neg((t00 * qu1 - s01 * qu0) / det);
+      k0 = ok ? k0 : T(0);
+      k1 = ok ? k1 : T(0);
+      f0 = ok ? f0 : T(0);
+      f1 = ok ? f1 : T(0);
+      if (valid) {
+        if (P.gain) {
+          P.gain[(((long long)k * 2 + 0) * n + c) * M + m] = k0;
+          P.gain[(((long long)k * 2 + 1) * n + c) * M + m] = k1;
+        }
+        if (c == 0) {
+          if (P.flag) P.flag[(long long)k * M + m] = ok ? 0 : 1;
+          if (P.ff) {
+            P.ff[((long long)k * 2 + 0) * M + m] = f0;
+            P.ff[((long long)k * 2 + 1) * M + m] = f1;
+          }
+        }
+        if (c == 1 && P.dv) {
+          P.dv[((long long)k * 2 + 0) * M + m] = f0 * qu0 + f1 * qu1;
+          P.dv[((long long)k * 2 + 1) * M + m] = T(0.5) * (((s00 * f0) * f0 + (s11 * f1) * f1) + T(2) * ((s01 * f0) * f1));
+        }
+      }
+      sK[(0 * n + c) * E + e] = k0;
+      sK[(1 * n + c) * E + e] = k1;
+      if (c == 0) {
+        sKf[0 * E + e] = f0;
+        sKf[1 * E + e] = f1;
+      }
+    }
+    __syncthreads();   // always: P' of a regularised trajectory needs the K of other columns, and its neighbour may be one
+    // phase 2b
+    if (col_lane) {
+#pragma unroll
+      for (int i = 0; i < n; ++i)
+        if (i <= c) {
+          T acc = sA[(0 * n + i) * E + e] * pv[0];
+#pragma unroll
+          for (int l = 1; l < n; ++l) acc = acc + sA[(l * n + i) * E + e] * pv[l];
+          const T gk = sG[(0 * (n + 2) + i) * E + e] * k0 + sG[(1 * (n + 2) + i) * E + e] * k1;
+          const T p0 = (sQ[i * n + c] + acc) - gk;
+          const T p1 = p0 - mu * (sK[(0 * n + i) * E + e] * k0 + sK[(1 * n + i) * E + e] * k1);
+          const T p = reg ? p1 : p0;
+          sP[(i * n + c) * E + e] = p;
+          sP[(c * n + i) * E + e] = p;
+        }
+      const T pj0 = gv + (sG[(0 * (n + 2) + c) * E + e] * f0 + sG[(1 * (n + 2) + c) * E + e] * f1);
+      const T pj1 = pj0 + mu * (k0 * f0 + k1 * f1);
+      sp[c * E + e] = reg ? pj1 : pj0;
+    } else if (P.weights) {
+      // row j = c - n of the knot's set: a = (a0 + alpha k) - K (x - x_k) on the raw observation slots, one lane per step size
+      const int j = c - n, D = P.D, nalpha = P.nalpha;
+      const long long lane = (long long)k * M + m, NM = (long long)nalpha * M;
+      T* w = P.weights + (((long long)k * 2 + j) * (D + 1)) * NM + m;
+      T acc = T(0);
+      bool first = true;
+#pragma unroll
+      for (int d = 0; d < OS2R_MAX_OBS; ++d)
+        if (d < D) {
+          const int sc = P.slot_col[d];
+          T wd = T(0);
+          if (sc >= 0) {
+            wd = lqr_neg(sK[(j * n + sc) * E + e]);
+            const T t = wd * P.obs[lane * D + d];
+            acc = first ? t : acc + t;
+            first = false;
+          }
+          if (valid)
+            for (int i = 0; i < nalpha; ++i) w[(long long)d * NM + (long long)i * M] = wd;
+        }
+      T a0 = P.actions[2 * lane + j];
+      a0 = a0 < T(-1) ? T(-1) : (a0 > T(1) ? T(1) : a0);
+      const T fj = sKf[j * E + e];
+      if (valid)
+        for (int i = 0; i < nalpha; ++i) w[(long long)D * NM + (long long)i * M] = (a0 + sAl[i] * fj) - acc;
+    }
+#pragma unroll
+    for (int l = 0; l < n; ++l) v[l] = vn[l];
+    gr = grn;
+  }
+
+  if (P.pmat_out || P.pvec_out) {
+    __syncthreads();
+    if (col_lane && valid) {
+      if (P.pmat_out) {
+#pragma unroll
+        for (int i = 0; i < n; ++i) P.pmat_out[(long long)(i * n + c) * M + m] = sP[(i * n + c) * E + e];
+      }
+      if (P.pvec_out) P.pvec_out[(long long)c * M + m] = sp[c * E + e];
+    }
+  }
+}
+
+// the launch (os2r_ilqr_mu_inst.hip, once per dtype): 1 if there is no kernel for this nq
+template <typename T>
+int launch_ilqr_backward_mu(int nq, const IlqrMuArgs<T>& args, hipStream_t stream);
+
+}  // namespace os2r

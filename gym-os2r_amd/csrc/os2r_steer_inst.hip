@@ -1,0 +1,22 @@
+// os2r_steer_inst.hip — the os2rt_ilqr_steer kernels (os2r_steer.hpp) of one dtype, chains of 2..5 dofs; compiled once per
+// OS2R_REAL into libos2r_steer.so.  They need no robot constants.
+#include "os2r_steer.hpp"
+
+#ifndef OS2R_REAL
+#error "OS2R_REAL must be float or double"
+#endif
+
+namespace os2r {
+
+using T = OS2R_REAL;
+
+template <>
+int launch_ilqr_steer<T>(int nq, const SteerArgs<T>& p, hipStream_t s) {
+  return by_chain_length(nq, [&](auto chain) {
+    constexpr int NQ = decltype(chain)::value;
+    const dim3 grid((unsigned)((p.base.M + kSearchTraj - 1) / kSearchTraj)), block(kSearchTraj * p.base.nalpha);
+    hipLaunchKernelGGL((ilqr_steer_kernel<T, NQ>), grid, block, 0, s, p);
+  });
+}
+
+}  // namespace os2r

@@ -705,37 +705,39 @@ class HipSim:
                 wts.permute(3, 0, 1, 2) if want_weights else None)
 
     # -- iLQR backward pass -----------------------------------------------------------------
-    def _ilqr_scalars(self, mu, alphas, want_weights):
-        """mu and alphas of ilqr_backward() -> (float, ctypes double array or None), checked."""
+    def _ilqr_scalars(self, mu, alphas, want_weights, what="ilqr_backward"):
+        """mu and alphas of ilqr_backward() (the alphas of ilqr_steer()) -> (float, ctypes double array or None), checked.
+        `what`: the method the errors name."""
         import math
         try:
             mu = float(mu)
         except (TypeError, ValueError):
-            raise ValueError(f"ilqr_backward: mu must be a number, got {type(mu)}") from None
+            raise ValueError(f"{what}: mu must be a number, got {type(mu)}") from None
         if not math.isfinite(mu) or mu < 0.0:
-            raise ValueError(f"ilqr_backward: mu must be finite and >= 0, got {mu}")
+            raise ValueError(f"{what}: mu must be finite and >= 0, got {mu}")
         if not want_weights:
             return mu, None
         try:
             al = [float(v) for v in (alphas.tolist() if hasattr(alphas, "tolist") else alphas)]
         except (TypeError, ValueError):
-            raise ValueError(f"ilqr_backward: alphas must be a sequence of numbers, got {type(alphas)}") from None
+            raise ValueError(f"{what}: alphas must be a sequence of numbers, got {type(alphas)}") from None
         if not 1 <= len(al) <= 16:
-            raise ValueError(f"ilqr_backward: between 1 and 16 alphas, got {len(al)}")
+            raise ValueError(f"{what}: between 1 and 16 alphas, got {len(al)}")
         if not all(math.isfinite(v) for v in al):
-            raise ValueError(f"ilqr_backward: every alpha must be finite, got {al}")
+            raise ValueError(f"{what}: every alpha must be finite, got {al}")
         return mu, (C.c_double * len(al))(*al)
 
     def ilqr_backward_into(self, A, B, Q, R, *, knots: int = 1, lx=None, lu=None, mu: float = 0.0, P_final=None, p_final=None,
                            gains_out=None, ff_out=None, P_out=None, p_out=None, flags_out=None, dv_out=None, actions=None, obs=None,
-                           alphas=None, weights_out=None):
+                           alphas=None, weights_out=None, mu_dev=None):
         """Allocation-free variant of ilqr_backward() on tensors in the kernel's layout (include/os2r_control.h:
         os2rc_ilqr_backward), the trajectory index fastest: with K = knots, L = K M and n = 2nq, A [n, n, L], B [n, 2, L],
         lx [n, L], lu [2, L], P_final [n, n, M], p_final [n, M] (each of the four None for its default), gains_out [K, 2, n, M],
         ff_out [K, 2, M], P_out [n, n, M] (may be P_final), p_out [n, M] (may be p_final), flags_out [K, M] uint8,
         dv_out [K, 2, M], weights_out [K, 2, D+1, len(alphas) M] with actions [L, 2], obs [L, D] and alphas; each output may be
-        None, not all of them but flags_out.  Shapes, dtypes, device and contiguity are checked before the library is called (it
-        takes addresses)."""
+        None, not all of them but flags_out.  mu_dev [M]: one mu per trajectory, read on the device (include/os2r_steer.h:
+        os2rt_ilqr_backward_mu; mu itself must then be 0).  Shapes, dtypes, device and contiguity are checked before the library is
+        called (it takes addresses)."""
         n = 2 * self.nq
         K = int(knots)
         if K < 1:
@@ -752,6 +754,9 @@ class HipSim:
         if weights_out is not None and (actions is None or obs is None or alphas is None):
             raise ValueError("ilqr_backward: weights need actions, obs (the point each knot was linearised about) and alphas")
         mu, al = self._ilqr_scalars(mu, alphas, weights_out is not None)
+        if mu_dev is not None and mu != 0.0:
+            raise ValueError(f"ilqr_backward: mu_dev and a nonzero mu ({mu}) are both given; the regularisation is one or the other")
+        self._out(mu_dev, (M,), self.dtype, "ilqr_backward: mu_dev")
         if B is None:
             raise ValueError("ilqr_backward: B is required")
         for t, shape, name in ((A, (n, n, L), "A"), (B, (n, 2, L), "B"), (lx, (n, L), "lx"), (lu, (2, L), "lu"),
@@ -768,9 +773,18 @@ class HipSim:
             self._out(obs, (L, self.D), self.dtype, "ilqr_backward: obs")
         else:
             actions = obs = None
+        lay = self._layout()
+        if mu_dev is not None:
+            from . import steer
+            lib = steer.load()
+            rc = lib.os2rt_ilqr_backward_mu(C.byref(lay), K, M, _ptr(A), _ptr(B), _ptr(lx), _ptr(lu), q, r, _ptr(mu_dev), _ptr(P_final),
+                                            _ptr(p_final), _ptr(gains_out), _ptr(ff_out), _ptr(P_out), _ptr(p_out), _ptr(flags_out),
+                                            _ptr(dv_out), _ptr(actions), _ptr(obs), al, nal, _ptr(weights_out), self._stream())
+            if rc != abi.OK:
+                raise Os2rError(f"os2rt_ilqr_backward_mu failed ({rc}): {lib.os2rt_last_error().decode()}")
+            return
         from . import control
         lib = control.load()
-        lay = self._layout()
         rc = lib.os2rc_ilqr_backward(C.byref(lay), K, M, _ptr(A), _ptr(B), _ptr(lx), _ptr(lu), q, r, mu, _ptr(P_final), _ptr(p_final),
                                      _ptr(gains_out), _ptr(ff_out), _ptr(P_out), _ptr(p_out), _ptr(flags_out), _ptr(dv_out), _ptr(actions),
                                      _ptr(obs), al, nal, _ptr(weights_out), self._stream())
@@ -779,7 +793,7 @@ class HipSim:
 
     def ilqr_backward(self, A, B, Q, R, *, knots, lx=None, lu=None, mu=0.0, P_final=None, p_final=None, actions=None, obs=None,
                       alphas=None, want_gains=True, want_ff=True, want_P=False, want_p=False, want_flags=True, want_dv=True,
-                      want_weights=False):
+                      want_weights=False, mu_dev=None):
         """The backward pass of iLQR for M = L / knots independent trajectories in one launch (include/os2r_control.h:
         os2rc_ilqr_backward; the arithmetic and its order are spelled out there): lqr_gains(sweeps=1) with its affine terms.
         A [L, 2nq, 2nq] and B [L, 2nq, 2] as linearize() returns them (taken without a copy), lane k * M + m knot k of trajectory
@@ -791,7 +805,10 @@ class HipSim:
         law of knot k is a = a_k + alpha ff_k - gains_k (x - x_k); flags is 1 where a knot's regularised 2 x 2 system was refused
         (gains and ff are 0 there); alpha dv[..., 0].sum(0) + alpha^2 dv[..., 1].sum(0) is the model's cost change under step size
         alpha.  weights (needs actions [L, 2], obs [L, D] and alphas) is the per-environment table rollout_schedule takes for a
-        handle of len(alphas) M environments, environment i M + m being trajectory m under alphas[i]."""
+        handle of len(alphas) M environments, environment i M + m being trajectory m under alphas[i].
+        mu_dev [M] (the handle's dtype, on its device, contiguous; mu must then be 0): one mu per trajectory, read on the device
+        -- the array ilqr_steer keeps up to date.  Trajectory m gets what mu = mu_dev[m] gives it, bit for bit; a negative or
+        non-finite entry runs as 0 with every knot of that trajectory refused (include/os2r_steer.h: os2rt_ilqr_backward_mu)."""
         n = 2 * self.nq
         K = int(knots)
         if K < 1:
@@ -801,7 +818,9 @@ class HipSim:
         if want_weights and (actions is None or obs is None or alphas is None):
             raise ValueError("ilqr_backward: weights need actions, obs (the point each knot was linearised about) and alphas")
         self._lqr_cost(Q, R, "ilqr_backward")
-        _, al = self._ilqr_scalars(mu, alphas, want_weights)
+        mu_host, al = self._ilqr_scalars(mu, alphas, want_weights)
+        if mu_dev is not None and mu_host != 0.0:
+            raise ValueError(f"ilqr_backward: mu_dev and a nonzero mu ({mu_host}) are both given; the regularisation is one or the other")
         for name, t, w in (("A", A, n), ("B", B, 2)):
             if not isinstance(t, torch.Tensor) or t.dim() != 3 or tuple(t.shape[1:]) != (n, w):
                 raise ValueError(f"ilqr_backward: {name} must be a tensor of shape (knots * M, {n}, {w}), got "
@@ -814,6 +833,7 @@ class HipSim:
         if L < K or L % K:
             raise ValueError(f"ilqr_backward: the {L} lanes of A are no multiple of knots = {K}")
         M = L // K
+        self._out(mu_dev, (M,), self.dtype, "ilqr_backward: mu_dev")
         a, b = A.permute(1, 2, 0).contiguous(), B.permute(1, 2, 0).contiguous()     # no copy for what linearize() returned
 
         def given(t, shape, name, perm):
@@ -841,7 +861,7 @@ class HipSim:
         dv = self._new(K, 2, M) if want_dv else None
         wts = self._new(K, 2, self.D + 1, nal * M) if want_weights else None
         self.ilqr_backward_into(a, b, Q, R, knots=K, lx=gx, lu=gu, mu=mu, P_final=pf, p_final=vf, gains_out=gains, ff_out=ff, P_out=pout,
-                                p_out=vout, flags_out=flags, dv_out=dv, actions=act, obs=ob, alphas=alphas, weights_out=wts)
+                                p_out=vout, flags_out=flags, dv_out=dv, actions=act, obs=ob, alphas=alphas, weights_out=wts, mu_dev=mu_dev)
         return (gains.permute(0, 3, 1, 2) if want_gains else None, ff.permute(0, 2, 1) if want_ff else None,
                 pout.permute(2, 0, 1) if want_P else None, vout.permute(1, 0) if want_p else None, flags,
                 dv.permute(0, 2, 1) if want_dv else None, wts.permute(3, 0, 1, 2) if want_weights else None)
@@ -932,6 +952,94 @@ class HipSim:
         self.ilqr_line_search_into(knot_obs, end_obs, actions, target, Q, R, cost=nominal["cost"], choice=choice, done=done, Q_final=Q_final,
                                    always=always, act_nom=nominal["actions"], obs_nom=nominal["obs"], end_nom=nominal["end_obs"],
                                    lx=nominal["lx"], lu=nominal["lu"], p_final=nominal["p_final"], index=index, cand_cost=cand_cost)
+        return choice, index, cand_cost, nominal
+
+    # -- iLQR line search that steers mu -----------------------------------------------------
+    def ilqr_steer_into(self, knot_obs, end_obs, actions, target, Q, R, dv, alphas, *, cost, mu, status, choice, iters=None, done=None,
+                        Q_final=None, rule=None, act_nom=None, obs_nom=None, end_nom=None, lx=None, lu=None, p_final=None, index=None,
+                        cand_cost=None, **rule_kw):
+        """Allocation-free steered line search of iLQR on tensors in the kernel's layouts (include/os2r_steer.h: os2rt_ilqr_steer;
+        the arithmetic and its order are spelled out there): ilqr_line_search_into, every argument of which but `always` is
+        taken as there, plus, per trajectory and in the same launch, an Armijo test on the predicted change, the update of mu, a
+        convergence test and a freeze.  dv [K, 2, M] as ilqr_backward_into wrote it, alphas the candidates' step sizes (host
+        values, one per candidate); mu [M] (the handle's dtype), status [M] int32 (0 active, 1 converged, 2 stalled) and iters [M]
+        int32 (or None) are read and written.  The rule is a dict and / or keywords over gym_os2r_amd.steer.RULE_DEFAULTS: armijo,
+        shrink, grow, mu_floor, mu_start, mu_max, tol.  Shapes, dtypes, device and contiguity are checked before the library is
+        called (it takes addresses)."""
+        from . import steer
+        what = "ilqr_steer"
+        n, D = 2 * self.nq, self.D
+        q, r = self._lqr_cost(Q, R, what)
+        qf = None if Q_final is None else self._lqr_cost(Q_final, R, f"{what}: Q_final")[0]
+        the_rule = steer.rule(rule, **rule_kw)
+        if not isinstance(target, torch.Tensor) or target.dim() != 2:
+            raise ValueError(f"{what}: target must be a tensor of shape (M, {D})")
+        if not isinstance(knot_obs, torch.Tensor) or knot_obs.dim() != 3:
+            raise ValueError(f"{what}: knot_obs must be a tensor of shape (K, nalpha * M, {D})")
+        M, K, N = int(target.shape[0]), int(knot_obs.shape[0]), int(knot_obs.shape[1])
+        if M < 1 or K < 1 or N < M or N % M:
+            raise ValueError(f"{what}: the {N} candidate lanes of knot_obs [{K} knots] are no multiple of the {M} trajectories of target")
+        nal, L = N // M, K * M
+        if not 1 <= nal <= 16:
+            raise ValueError(f"{what}: between 1 and 16 candidates per trajectory, got {nal}")
+        if K * N > 2 ** 31 - 1:
+            raise ValueError(f"{what}: {K} knots of {N} candidate lanes exceed what an int32 index addresses")
+        al = self._ilqr_scalars(0.0, alphas, True, what)[1]
+        if len(al) != nal:
+            raise ValueError(f"{what}: {len(al)} alphas for {nal} candidates per trajectory")
+        if any(t is None for t in (end_obs, actions, dv, cost, mu, status, choice)):
+            raise ValueError(f"{what}: end_obs, actions, dv, cost, mu, status and choice are required")
+        for t, shape, name in ((knot_obs, (K, N, D), "knot_obs"), (end_obs, (N, D), "end_obs"), (actions, (K, N, 2), "actions"),
+                               (target, (M, D), "target"), (dv, (K, 2, M), "dv"), (cost, (M,), "cost"), (mu, (M,), "mu"),
+                               (act_nom, (K, M, 2), "act_nom"), (obs_nom, (K, M, D), "obs_nom"), (end_nom, (M, D), "end_nom"),
+                               (lx, (n, L), "lx"), (lu, (2, L), "lu"), (p_final, (n, M), "p_final"), (cand_cost, (nal, M), "cand_cost")):
+            self._out(t, shape, self.dtype, f"{what}: {name}")
+        self._out(done, (K, N), torch.uint8, f"{what}: done")
+        for t, shape, name in ((status, (M,), "status"), (iters, (M,), "iters"), (choice, (M,), "choice"), (index, (L,), "index")):
+            self._out(t, shape, torch.int32, f"{what}: {name}")
+        lib = steer.load()
+        lay = self._layout()
+        rc = lib.os2rt_ilqr_steer(C.byref(lay), K, M, nal, _ptr(knot_obs), _ptr(end_obs), _ptr(actions), _ptr(done), _ptr(target), q, r, qf,
+                                  _ptr(dv), al, C.byref(the_rule), _ptr(cost), _ptr(act_nom), _ptr(obs_nom), _ptr(end_nom), _ptr(lx), _ptr(lu),
+                                  _ptr(p_final), _ptr(mu), _ptr(status), _ptr(iters), _ptr(choice), _ptr(index), _ptr(cand_cost),
+                                  self._stream())
+        if rc != abi.OK:
+            raise Os2rError(f"os2rt_ilqr_steer failed ({rc}): {lib.os2rt_last_error().decode()}")
+
+    def ilqr_steer(self, knot_obs, end_obs, actions, target, Q, R, dv, alphas, *, nominal, done=None, Q_final=None, rule=None,
+                   want_cand_cost: bool = True, **rule_kw):
+        """The line search of iLQR for M trajectories that also steers every trajectory's regularisation, in one launch
+        (include/os2r_steer.h: os2rt_ilqr_steer): ilqr_line_search on the nominal an earlier call returned, with, per trajectory,
+        an Armijo test of the actual against the predicted change alpha dv[..., 0].sum(0) + alpha^2 dv[..., 1].sum(0) (rule
+        member armijo; 0: none), mu halved after an accepted step and raised after an iteration without one (shrink, grow,
+        mu_floor, mu_start, mu_max), a trajectory frozen once a step lowered its cost by no more than tol |cost| (status 1) or
+        its mu would pass mu_max (status 2).  dv [K, M, 2] as ilqr_backward returned it (its permuted view of the kernel's layout
+        is taken without a copy), alphas the step sizes ilqr_backward made the candidates' table for.  `nominal` is the dict
+        ilqr_line_search returned; mu [M] (zeros), status [M] int32 (zeros: active) and iters [M] int32 (zeros) are added to it
+        where missing and updated in place like the rest -- nominal["mu"] is what ilqr_backward(mu_dev=...) reads.  No host
+        value is read: iterations can be launched back to back.
+        -> (choice [M] int32: the accepted candidate or -1, index [K M] int32 for knots.copy_envs_from(cand_knots, index),
+        cand_cost [nalpha, M] or None, nominal)."""
+        what = "ilqr_steer"
+        if not isinstance(target, torch.Tensor) or target.dim() != 2 or not isinstance(knot_obs, torch.Tensor) or knot_obs.dim() != 3:
+            raise ValueError(f"{what}: target must be a tensor of shape (M, {self.D}) and knot_obs one of shape (K, nalpha * M, {self.D})")
+        M, K, N = int(target.shape[0]), int(knot_obs.shape[0]), int(knot_obs.shape[1])
+        if M < 1 or K < 1 or N < M or N % M:
+            raise ValueError(f"{what}: the {N} candidate lanes of knot_obs [{K} knots] are no multiple of the {M} trajectories of target")
+        if not isinstance(nominal, dict) or any(k not in nominal for k in ("cost", "actions", "obs", "end_obs", "lx", "lu", "p_final")):
+            raise ValueError(f"{what}: nominal must be the dict ilqr_line_search (or an earlier call) returned")
+        if not isinstance(dv, torch.Tensor) or tuple(dv.shape) != (K, M, 2) or dv.dtype != self.dtype or dv.device != self.device:
+            raise ValueError(f"{what}: dv must be a {self.dtype} tensor of shape ({K}, {M}, 2) on {self.device}, as ilqr_backward returns it")
+        dv_k = dv.permute(0, 2, 1).contiguous()             # no copy for what ilqr_backward returned
+        for name, dtype in (("mu", self.dtype), ("status", torch.int32), ("iters", torch.int32)):
+            if nominal.get(name) is None:
+                nominal[name] = torch.zeros(M, dtype=dtype, device=self.device)
+        choice, index = self._new(M, dtype=torch.int32), self._new(K * M, dtype=torch.int32)
+        cand_cost = self._new(N // M, M) if want_cand_cost else None
+        self.ilqr_steer_into(knot_obs, end_obs, actions, target, Q, R, dv_k, alphas, cost=nominal["cost"], mu=nominal["mu"],
+                             status=nominal["status"], choice=choice, iters=nominal["iters"], done=done, Q_final=Q_final, rule=rule,
+                             act_nom=nominal["actions"], obs_nom=nominal["obs"], end_nom=nominal["end_obs"], lx=nominal["lx"],
+                             lu=nominal["lu"], p_final=nominal["p_final"], index=index, cand_cost=cand_cost, **rule_kw)
         return choice, index, cand_cost, nominal
 
     def action_violations_into(self, dst: torch.Tensor, clear: bool = True):
