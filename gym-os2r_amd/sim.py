@@ -1042,6 +1042,107 @@ class HipSim:
                              lu=nominal["lu"], p_final=nominal["p_final"], index=index, cand_cost=cand_cost, **rule_kw)
         return choice, index, cand_cost, nominal
 
+    # -- MPPI update ------------------------------------------------------------------------
+    def mppi_update_into(self, returns, actions, nominal_in, nominal_out, *, samples: int, temperature: float, shift: int = 1,
+                         tail: str = "hold", applied=None, table=None, weights=None, ess=None, count=None):
+        """Allocation-free MPPI update on tensors in the kernel's layouts (include/os2r_mppi.h: os2rm_mppi_update; the arithmetic
+        and its order are spelled out there).  With S = samples, M robots, N = S M lanes (lane s M + m: sample s of robot m) and K
+        knots: returns [N], actions [K, N, 2] and nominal_in [K, M, 2] are read; nominal_out [K, M, 2] (required, another tensor
+        than nominal_in), applied [M, 2], table [K, 2, D+1, N] (only its bias entries [:, :, D, :] are written), weights [S, M],
+        ess [M] and count [M] int32 are written, each of the last five or None.  temperature > 0 is the softmax temperature of
+        the returns (beta = 1 / temperature), shift in 0..K, tail "hold" or "zero".  Shapes, dtypes, device and contiguity are
+        checked before the library is called (it takes addresses)."""
+        import math
+        from . import mppi
+        what = "mppi_update"
+        if isinstance(samples, bool) or not isinstance(samples, int) or samples < 1:
+            raise ValueError(f"{what}: samples must be an integer >= 1, got {samples!r}")
+        try:
+            temp = float(temperature)
+        except (TypeError, ValueError):
+            raise ValueError(f"{what}: temperature must be a number, got {type(temperature)}") from None
+        if not math.isfinite(temp) or temp <= 0.0 or not math.isfinite(1.0 / temp):
+            raise ValueError(f"{what}: temperature must be finite and > 0, got {temp}")
+        if tail not in mppi.TAILS:
+            raise ValueError(f"{what}: tail must be 'hold' or 'zero', got {tail!r}")
+        if not isinstance(actions, torch.Tensor) or actions.dim() != 3:
+            raise ValueError(f"{what}: actions must be a tensor of shape (K, samples * M, 2)")
+        K, N, S = int(actions.shape[0]), int(actions.shape[1]), samples
+        if K < 1 or N < S or N % S:
+            raise ValueError(f"{what}: the {N} lanes of actions [{K} knots] are no multiple of samples = {S}")
+        M = N // S
+        if isinstance(shift, bool) or not isinstance(shift, int) or not 0 <= shift <= K:
+            raise ValueError(f"{what}: shift must be an integer in 0..{K}, got {shift!r}")
+        if returns is None or nominal_in is None or nominal_out is None:
+            raise ValueError(f"{what}: returns, nominal_in and nominal_out are required")
+        for t, shape, name in ((returns, (N,), "returns"), (actions, (K, N, 2), "actions"), (nominal_in, (K, M, 2), "nominal_in"),
+                               (nominal_out, (K, M, 2), "nominal_out"), (applied, (M, 2), "applied"),
+                               (table, (K, 2, self.D + 1, N), "table"), (weights, (S, M), "weights"), (ess, (M,), "ess")):
+            self._out(t, shape, self.dtype, f"{what}: {name}")
+        self._out(count, (M,), torch.int32, f"{what}: count")
+        if nominal_out.data_ptr() == nominal_in.data_ptr():
+            raise ValueError(f"{what}: nominal_out must be another tensor than nominal_in (every slot reads its source slot itself)")
+        lib = mppi.load()
+        lay = self._layout()
+        rc = lib.os2rm_mppi_update(C.byref(lay), K, M, S, _ptr(returns), _ptr(actions), _ptr(nominal_in), 1.0 / temp, shift,
+                                   mppi.TAILS[tail], _ptr(nominal_out), _ptr(applied), _ptr(table), _ptr(weights), _ptr(ess), _ptr(count),
+                                   self._stream())
+        if rc != abi.OK:
+            raise Os2rError(f"os2rm_mppi_update failed ({rc}): {lib.os2rm_last_error().decode()}")
+
+    def mppi_update(self, returns, actions, nominal, *, samples: int, temperature: float, shift: int = 1, tail: str = "hold",
+                    table=None, want_weights: bool = False, want_ess: bool = False):
+        """The MPPI update of M robots in one launch (include/os2r_mppi.h: os2rm_mppi_update): with S = samples and N = S M lanes,
+        lane s M + m sample s of robot m -- a planner handle forked by copy_envs_from(real, arange(N) % M) --, returns [N] and
+        actions [K, N, 2] are what the noisy rollout_schedule(first_episode=True, want_actions=True) returned and nominal
+        [K, M, 2] the nominal its table held.  Every robot's lanes with a finite return are weighted by
+        exp((return - max) / temperature); the new nominal is the weighted mean of their action sequences clipped to [-1, 1] (a
+        robot without a valid lane keeps its nominal), moved `shift` slots towards the present with the last slot held
+        (tail="hold") or zeros behind it (tail="zero").
+        table: None (no table), True (this handle's own [N, K, 2, D+1] table, allocated as zeros at the first call and kept) or
+        the table an earlier call or ilqr_backward(want_weights=True) returned -- a permuted view of the kernel's
+        [K, 2, D+1, N] layout; only its bias entries table[:, :, :, D] are written, to the new nominal of the lane's robot: the
+        weights of the next rollout_schedule, which then applies clip(nominal + sigma eps).
+        The new nominal is written into one of two buffers the handle keeps for this shape, the one `nominal` is not: feed it
+        back and the two alternate.
+        -> (applied [M, 2]: slot 0 of the weighted mean, the action for real.step; nominal [K, M, 2]; table [N, K, 2, D+1] | None;
+        weights [S, M] | None: the unnormalised weights; ess [M] | None: the effective sample size; count [M] int32: the valid
+        lanes of every robot)."""
+        what = "mppi_update"
+        if not isinstance(actions, torch.Tensor) or actions.dim() != 3:
+            raise ValueError(f"{what}: actions must be a tensor of shape (K, samples * M, 2)")
+        if isinstance(samples, bool) or not isinstance(samples, int) or samples < 1:
+            raise ValueError(f"{what}: samples must be an integer >= 1, got {samples!r}")
+        K, N, S = int(actions.shape[0]), int(actions.shape[1]), samples
+        if K < 1 or N < S or N % S:
+            raise ValueError(f"{what}: the {N} lanes of actions [{K} knots] are no multiple of samples = {S}")
+        M, R = N // S, self.D + 1
+        self._out(nominal, (K, M, 2), self.dtype, f"{what}: nominal")
+        if nominal is None:
+            raise ValueError(f"{what}: nominal is required")
+        tab = None
+        if table is True:
+            tables = self.__dict__.setdefault("_mppi_tables", {})
+            if (K, N) not in tables:
+                tables[(K, N)] = torch.zeros(K, 2, R, N, dtype=self.dtype, device=self.device)
+            tab = tables[(K, N)]
+        elif table is not None and table is not False:
+            if (not isinstance(table, torch.Tensor) or tuple(table.shape) != (N, K, 2, R) or table.dtype != self.dtype
+                    or table.device != self.device or not table.permute(1, 2, 3, 0).is_contiguous()):
+                raise ValueError(f"{what}: table must be None, True or a {self.dtype} tensor of shape ({N}, {K}, 2, {R}) on {self.device} "
+                                 f"that is a permuted view of the kernel's [K, 2, D+1, N] layout, as an earlier call returned it")
+            tab = table.permute(1, 2, 3, 0)
+        pair = self.__dict__.setdefault("_mppi_nominals", {})
+        if (K, M) not in pair:
+            pair[(K, M)] = (self._new(K, M, 2), self._new(K, M, 2))
+        out = pair[(K, M)][0] if nominal.data_ptr() != pair[(K, M)][0].data_ptr() else pair[(K, M)][1]
+        applied, count = self._new(M, 2), self._new(M, dtype=torch.int32)
+        weights = self._new(S, M) if want_weights else None
+        ess = self._new(M) if want_ess else None
+        self.mppi_update_into(returns, actions, nominal, out, samples=S, temperature=temperature, shift=shift, tail=tail,
+                              applied=applied, table=tab, weights=weights, ess=ess, count=count)
+        return applied, out, (None if tab is None else tab.permute(3, 0, 1, 2)), weights, ess, count
+
     def action_violations_into(self, dst: torch.Tensor, clear: bool = True):
         """Copy the running count of out-of-range caller actions into ``dst`` (one int32/uint32 element,
         device or pinned host memory) on the current stream; nothing waits."""
