@@ -579,9 +579,12 @@ constexpr int kPinDs = 0x1 | 0x2 | 0x4 | 0x8 | 0x10 | 0x20 | 0x40 | 0x400;
 // Opaque copy: a fresh SSA value the optimiser cannot merge with earlier uses.  Used to
 // *re*-compute cheap quantities (a joint rotation is 12 FMAs) instead of holding them in
 // registers across the whole physics iteration: fp64 state is register hungry and anything
-// beyond 512 registers per lane spills to scratch, i.e. to HBM.
+// beyond 512 registers per lane spills to scratch, i.e. to HBM.  Also the pin that keeps a product or a
+// value handed from one pass to the next a plain value (no fusing across it).
 __device__ __forceinline__ double opaque(double x) { asm volatile("" : "+v"(x)); return x; }
 __device__ __forceinline__ float opaque(float x) { asm volatile("" : "+v"(x)); return x; }
+// An empty instruction the optimiser may not move, taking x where a store of x would
+template <typename T> __device__ __forceinline__ void pin_use(T x) { asm volatile("" :: "v"(x)); }
 
 // One of three values by a wave-uniform index.  With a compile-time index it folds to the value; with a run-time one
 // (the generic kernels: the joint axis is data) it stays two selects -- indexing a local array with it would put
@@ -693,9 +696,13 @@ __device__ __forceinline__ void substep(const MD& md, const Params<T, MD, DR>& p
   OS2R_STAMP(0);
   // Per-lane LDS slots (slot-major: lds[slot * 64 + lane], conflict free).  During the
   // articulated-body passes they hold the per-joint quantities that must survive from one pass
-  // to the next (U = I^A S, 1/D, u); afterwards the same storage holds the triangular factor of
-  // the inverse mass matrix (mirror for the contact-row set-up).  Keeping these out of the
-  // register file is what keeps the fp64 kernel free of scratch spills.
+  // to the next (U = I^A S, 1/D, u) for the joints at and above kKeep; afterwards the same storage holds the
+  // triangular factor of the inverse mass matrix (mirror for the contact-row set-up).
+  // Joints below kKeep hand these eight values over in registers (round 7): the compiled-in robots all of them (the
+  // 5-dof fp64 kernels hold them without scratch, the fp32 ones inside 256 registers), the run-time-model kernels none.
+  constexpr int kKeep = MD::kStatic ? NQ : 0;
+  V3<T> keepUa[kKeep > 0 ? kKeep : 1], keepUl[kKeep > 0 ? kKeep : 1];
+  T keepDi[kKeep > 0 ? kKeep : 1], keepU[kKeep > 0 ? kKeep : 1];
   const int lane_ = threadIdx.x;
   auto L = [&](int slot) -> T& { return lds[slot * kWave + lane_]; };
   constexpr int kUa = 0, kUl = 3 * NQ, kDi = 6 * NQ, kU = 7 * NQ;  // 8*NQ slots
@@ -777,10 +784,22 @@ __device__ __forceinline__ void substep(const MD& md, const Params<T, MD, DR>& p
       if (i == md.act_dof(0)) tau = tau_hip;
       if (i == md.act_dof(1)) tau = tau_knee;
       const T u = tau - damp * qd[i] - comp(pAn, ax);
-      stv(kUa, i, Ua);
-      stv(kUl, i, Ul);
-      L(kDi + i) = Dinv;
-      L(kU + i) = u;
+      if (i < kKeep) {
+        // One empty asm per value where its store was, and in `request` one where its load was: the optimiser orders the
+        // operands of a sum by the position of the last instruction it may not move among their sources, and which product of
+        // `a b + c d` is fused into the FMA follows that order.  With a pin in the place of every store and load the order,
+        // and with it every rounding, is what it was with the LDS round trip (docs/studies/round7_aba_handover.md 3).
+        keepUa[i] = Ua; keepUl[i] = Ul; keepDi[i] = Dinv; keepU[i] = u;
+        pin_use(Ua.x); pin_use(Ua.y); pin_use(Ua.z);
+        pin_use(Ul.x); pin_use(Ul.y); pin_use(Ul.z);
+        pin_use(Dinv);
+        pin_use(u);
+      } else {
+        stv(kUa, i, Ua);
+        stv(kUl, i, Ul);
+        L(kDi + i) = Dinv;
+        L(kU + i) = u;
+      }
       if (i > 0) {
         // Ia = I^A - U U^T / D
         const V3<T> ka = Dinv * Ua, kl = Dinv * Ul;
@@ -853,16 +872,22 @@ __device__ __forceinline__ void substep(const MD& md, const Params<T, MD, DR>& p
   V3<T> hua[2], hul[2];
   {
     V3<T> aa = mk<T>(0, 0, 0), al = mk<T>(0, 0, -par.gravity());
-    auto request = [&](int i, int b) { hu[b] = L(kU + i); hua[b] = ldv(kUa, i); hul[b] = ldv(kUl, i); hd[b] = L(kDi + i); };
-    auto arrived = [&](int b) {
+    // (a joint below kKeep is taken from its registers, through a pin where each load was: nothing to wait for)
+    auto pinv = [&](V3<T> x) { return mk(opaque(x.x), opaque(x.y), opaque(x.z)); };
+    auto request = [&](int i, int b) {
+      if (i < kKeep) { hu[b] = opaque(keepU[i]); hua[b] = pinv(keepUa[i]); hul[b] = pinv(keepUl[i]); hd[b] = opaque(keepDi[i]); }
+      else { hu[b] = L(kU + i); hua[b] = ldv(kUa, i); hul[b] = ldv(kUl, i); hd[b] = L(kDi + i); }
+    };
+    auto arrived = [&](int i, int b) {
       asm volatile("" : "+v"(hu[b]), "+v"(hd[b]), "+v"(hua[b].x), "+v"(hua[b].y), "+v"(hua[b].z), "+v"(hul[b].x), "+v"(hul[b].y), "+v"(hul[b].z));
-      asm volatile("" ::: "memory");
+      if (i < kKeep) asm volatile("");
+      else asm volatile("" ::: "memory");
     };
     request(0, 0);
 #pragma unroll
     for (int i = 0; i < NQ; ++i) {
       const int b = i & 1;
-      arrived(b);
+      arrived(i, b);
       if (i + 1 < NQ) request(i + 1, b ^ 1);
       const int ax = md.axis(i);
       const V3<T> r = mk(md.rpos(i, 0), md.rpos(i, 1), md.rpos(i, 2));
@@ -902,10 +927,15 @@ __device__ __forceinline__ void substep(const MD& md, const Params<T, MD, DR>& p
     // right in front of their first use, and a lone wave waited out every round trip (five times ~100 cycles per iteration)
     V3<T> mUa[2], mUl[2];
     T mdi[2];
-    auto request_m = [&](int i, int b) { mUa[b] = ldv(kUa, i); mUl[b] = ldv(kUl, i); mdi[b] = L(kDi + i); };
-    auto arrived_m = [&](int b) {
+    auto pinv = [&](V3<T> x) { return mk(opaque(x.x), opaque(x.y), opaque(x.z)); };
+    auto request_m = [&](int i, int b) {
+      if (i < kKeep) { mUa[b] = pinv(keepUa[i]); mUl[b] = pinv(keepUl[i]); mdi[b] = opaque(keepDi[i]); }
+      else { mUa[b] = ldv(kUa, i); mUl[b] = ldv(kUl, i); mdi[b] = L(kDi + i); }
+    };
+    auto arrived_m = [&](int i, int b) {
       asm volatile("" : "+v"(mdi[b]), "+v"(mUa[b].x), "+v"(mUa[b].y), "+v"(mUa[b].z), "+v"(mUl[b].x), "+v"(mUl[b].y), "+v"(mUl[b].z));
-      asm volatile("" ::: "memory");
+      if (i < kKeep) asm volatile("");
+      else asm volatile("" ::: "memory");
     };
     // (the last joint's U and 1/D are still in the registers of the outward pass above.  fp64 only: the fp32 kernels are
     // built for two waves per SIMD, which hide the round trips, and have no registers to spare)
@@ -914,7 +944,7 @@ __device__ __forceinline__ void substep(const MD& md, const Params<T, MD, DR>& p
 #pragma unroll
     for (int i = NQ - 1; i >= 0; --i) {
       if constexpr (kAhead) {
-        if (i < NQ - 1) arrived_m(i & 1);
+        if (i < NQ - 1) arrived_m(i, i & 1);
         if (i > 0) { request_m(i - 1, (i - 1) & 1); __builtin_amdgcn_sched_barrier(kPinDs); }
       } else {
         request_m(i, i & 1);
