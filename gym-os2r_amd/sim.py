@@ -1143,6 +1143,88 @@ class HipSim:
                               applied=applied, table=tab, weights=weights, ess=ess, count=count)
         return applied, out, (None if tab is None else tab.permute(3, 0, 1, 2)), weights, ess, count
 
+    # -- particle-filter update -------------------------------------------------------------
+    def pf_update_into(self, obs, meas, prec, logw_out, index, *, particles: int, logw_in=None, u=None, resample_ratio: float = 0.5,
+                       est=None, weights=None, ess=None, count=None, resampled=None):
+        """Allocation-free particle-filter update on tensors in the kernel's layouts (include/os2r_pf.h: os2rp_pf_update; the
+        arithmetic and its order are spelled out there).  With S = particles, M robots and N = S M lanes (lane s M + m: particle s
+        of robot m): obs [N, D], meas [M, D], prec [D], logw_in [S, M] (None: zeros) and u [M] (None: 0.5) are read; logw_out
+        [S, M] (required, another tensor than logw_in), index [N] int32 (required), est [M, D], weights [S, M], ess [M], count [M]
+        int32 and resampled [M] int32 are written, each of the last five or None.  resample_ratio is finite and >= 0.  Shapes,
+        dtypes, device and contiguity are checked before the library is called (it takes addresses)."""
+        import math
+        from . import pf
+        what = "pf_update"
+        if isinstance(particles, bool) or not isinstance(particles, int) or particles < 1:
+            raise ValueError(f"{what}: particles must be an integer >= 1, got {particles!r}")
+        try:
+            ratio = float(resample_ratio)
+        except (TypeError, ValueError):
+            raise ValueError(f"{what}: resample_ratio must be a number, got {type(resample_ratio)}") from None
+        if isinstance(resample_ratio, bool) or not math.isfinite(ratio) or ratio < 0.0:
+            raise ValueError(f"{what}: resample_ratio must be finite and >= 0, got {resample_ratio!r}")
+        if not isinstance(obs, torch.Tensor) or obs.dim() != 2:
+            raise ValueError(f"{what}: obs must be a tensor of shape (particles * M, {self.D})")
+        N, S = int(obs.shape[0]), particles
+        if N < S or N % S:
+            raise ValueError(f"{what}: the {N} lanes of obs are no multiple of particles = {S}")
+        M = N // S
+        if meas is None or prec is None or logw_out is None or index is None:
+            raise ValueError(f"{what}: obs, meas, prec, logw_out and index are required")
+        for t, shape, name in ((obs, (N, self.D), "obs"), (meas, (M, self.D), "meas"), (prec, (self.D,), "prec"), (logw_in, (S, M), "logw_in"),
+                               (u, (M,), "u"), (logw_out, (S, M), "logw_out"), (est, (M, self.D), "est"), (weights, (S, M), "weights"),
+                               (ess, (M,), "ess")):
+            self._out(t, shape, self.dtype, f"{what}: {name}")
+        for t, shape, name in ((index, (N,), "index"), (count, (M,), "count"), (resampled, (M,), "resampled")):
+            self._out(t, shape, torch.int32, f"{what}: {name}")
+        if logw_in is not None and logw_out.data_ptr() == logw_in.data_ptr():
+            raise ValueError(f"{what}: logw_out must be another tensor than logw_in (the launch keeps the weights in it between its passes)")
+        lib = pf.load()
+        lay = self._layout()
+        rc = lib.os2rp_pf_update(C.byref(lay), M, S, _ptr(obs), _ptr(meas), _ptr(prec), _ptr(logw_in), _ptr(u), ratio, _ptr(logw_out),
+                                 _ptr(index), _ptr(est), _ptr(weights), _ptr(ess), _ptr(count), _ptr(resampled), self._stream())
+        if rc != abi.OK:
+            raise Os2rError(f"os2rp_pf_update failed ({rc}): {lib.os2rp_last_error().decode()}")
+
+    def pf_update(self, obs, meas, prec, *, particles: int, logw=None, u=None, resample_ratio: float = 0.5, want_estimate: bool = True,
+                  want_weights: bool = False):
+        """The particle-filter update of M robots in one launch (include/os2r_pf.h: os2rp_pf_update): with S = particles and
+        N = S M lanes, lane s M + m particle s of robot m -- a particle handle forked by copy_envs_from(real, arange(N) % M) --,
+        obs [N, D] is every particle's observation as step, a one-step rollout or copy_envs_from returned it, meas [M, D] the
+        measurement of every robot and prec [D] one inverse variance per observation entry (0 drops the entry).  Every particle's
+        log-weight is logw [S, M] (None: zeros) minus half its precision-weighted squared distance from the measurement; a
+        particle whose log-weight is not finite is invalid and has weight 0.  A robot resamples when its effective sample size
+        falls below resample_ratio * S or when it holds an invalid particle: systematic resampling with the offset u [M] in
+        [0, 1) (None: 0.5), after which its log-weights are 0.  A robot without a valid particle is lost: nothing moves, its
+        log-weights are 0 and its estimate is the measurement.
+        The new log-weights are written into one of two buffers the handle keeps for this shape, the one `logw` is not: feed
+        them back and the two alternate.
+        -> (logw [S, M]: normalised to a maximum of 0, -inf for an invalid particle; index [N] int32 for
+        self.copy_envs_from(self, index): the ancestor of every lane, -1 (keep) in the lanes of a robot that did not resample;
+        est [M, D] | None: the weighted mean observation; weights [S, M] | None: the unnormalised weights; ess [M]: the effective
+        sample size; count [M] int32: the valid particles of every robot; resampled [M] int32: 1 where the robot resampled)."""
+        what = "pf_update"
+        if isinstance(particles, bool) or not isinstance(particles, int) or particles < 1:
+            raise ValueError(f"{what}: particles must be an integer >= 1, got {particles!r}")
+        if not isinstance(obs, torch.Tensor) or obs.dim() != 2:
+            raise ValueError(f"{what}: obs must be a tensor of shape (particles * M, {self.D})")
+        N, S = int(obs.shape[0]), particles
+        if N < S or N % S:
+            raise ValueError(f"{what}: the {N} lanes of obs are no multiple of particles = {S}")
+        M = N // S
+        self._out(logw, (S, M), self.dtype, f"{what}: logw")
+        pair = self.__dict__.setdefault("_pf_logw", {})
+        if (S, M) not in pair:
+            pair[(S, M)] = (self._new(S, M), self._new(S, M))
+        out = pair[(S, M)][0] if logw is None or logw.data_ptr() != pair[(S, M)][0].data_ptr() else pair[(S, M)][1]
+        index = self._new(N, dtype=torch.int32)
+        est = self._new(M, self.D) if want_estimate else None
+        weights = self._new(S, M) if want_weights else None
+        ess, count, resampled = self._new(M), self._new(M, dtype=torch.int32), self._new(M, dtype=torch.int32)
+        self.pf_update_into(obs, meas, prec, out, index, particles=S, logw_in=logw, u=u, resample_ratio=resample_ratio, est=est,
+                            weights=weights, ess=ess, count=count, resampled=resampled)
+        return out, index, est, weights, ess, count, resampled
+
     def action_violations_into(self, dst: torch.Tensor, clear: bool = True):
         """Copy the running count of out-of-range caller actions into ``dst`` (one int32/uint32 element,
         device or pinned host memory) on the current stream; nothing waits."""
