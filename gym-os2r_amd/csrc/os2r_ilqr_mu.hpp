@@ -12,39 +12,16 @@
 // No lane indexes a register array at run time, nothing goes to scratch (tests/test_ilqr_steer_host.py reads the metadata).
 //
 // The arithmetic is the contract of include/os2r_control.h, steps 1-10, with mu read per trajectory (include/os2r_steer.h).
+//
+// The kernel below is still a copy of os2r_ilqr.hpp's text, against the rule of DESIGN.md section 4: as one function template
+// with a compile-time switch, the plain fp64 kernel measured 0.3 to 0.7 % slower at mu != 0 in both forms of the template
+// that were timed (profiles/refactor_bodies_ab.txt).  Whoever changes one of the two texts changes the other.
 #pragma once
 #include "os2r_ilqr.hpp"
+#include "os2r_bits.hpp"   // steer_invalid
 #include "../../include/os2r_steer.h"
 
 namespace os2r {
-
-// The bits of a value, through an empty asm on the INTEGER: what comes out has no floating-point history, so the class tests below
-// are compiled as written.  (The libraries are built without NaN / infinity semantics; a bit test of a float that passed
-// through an asm as a float -- lqr_finite -- is still recognised as a class test of that float and folded away: DESIGN.md
-// section 4 has what the assembly holds in its place.)
-__device__ __forceinline__ unsigned steer_bits(float x) {
-  unsigned b = (unsigned)__float_as_int(x);
-  asm volatile("" : "+v"(b));
-  return b;
-}
-__device__ __forceinline__ unsigned long long steer_bits(double x) {
-  unsigned long long b = (unsigned long long)__double_as_longlong(x);
-  asm volatile("" : "+v"(b));
-  return b;
-}
-__device__ __forceinline__ bool steer_finite(float x) { return (steer_bits(x) >> 23 & 0xffu) != 0xffu; }
-__device__ __forceinline__ bool steer_finite(double x) { return (steer_bits(x) >> 52 & 0x7ffull) != 0x7ffull; }
-__device__ __forceinline__ bool steer_nan(float x) { return (steer_bits(x) & 0x7fffffffu) > 0x7f800000u; }
-__device__ __forceinline__ bool steer_nan(double x) { return (steer_bits(x) & 0x7fffffffffffffffull) > 0x7ff0000000000000ull; }
-// negative, or not finite: by the sign bit of a value that is no zero
-__device__ __forceinline__ bool steer_invalid(float x) {
-  const unsigned b = steer_bits(x);
-  return (b >> 23 & 0xffu) == 0xffu || (b >> 31 != 0u && (b & 0x7fffffffu) != 0u);
-}
-__device__ __forceinline__ bool steer_invalid(double x) {
-  const unsigned long long b = steer_bits(x);
-  return (b >> 52 & 0x7ffull) == 0x7ffull || (b >> 63 != 0ull && (b & 0x7fffffffffffffffull) != 0ull);
-}
 
 template <typename T>
 struct IlqrMuArgs {

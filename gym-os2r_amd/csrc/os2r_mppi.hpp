@@ -21,9 +21,7 @@
 // The arithmetic is the contract of include/os2r_mppi.h: the layout's dtype, no contraction, each partial in ascending order.
 // tests/test_mppi_host.py restates it in numpy; tests/test_gpu_mppi.py compares bit for bit.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
+#include "os2r_partials.hpp"
 #include "../../include/os2r_mppi.h"
 
 namespace os2r {
@@ -53,31 +51,13 @@ struct alignas(2 * sizeof(T)) MppiPair {
   T x, y;
 };
 
-// The library is built with -fno-honor-nans -fno-honor-infinities: a return is found finite or not by its exponent bits, and
-// the word that holds them passes through an empty asm as an integer.  (Hiding the floating-point value alone is not enough
-// here: the compiler recognises the mask-and-compare on its bits as a class test and, told that there are neither NaNs nor
-// infinities, folds it to true -- the first build counted every lane valid.)
-__device__ __forceinline__ unsigned mppi_opaque_bits(unsigned b) { asm volatile("" : "+v"(b)); return b; }
-__device__ __forceinline__ bool mppi_finite(double x) { return (mppi_opaque_bits((unsigned)__double2hiint(x)) >> 20 & 0x7ffu) != 0x7ffu; }
-__device__ __forceinline__ bool mppi_finite(float x) { return (mppi_opaque_bits((unsigned)__float_as_int(x)) >> 23 & 0xffu) != 0xffu; }
-__device__ __forceinline__ double mppi_exp(double x) { return ::exp(x); }
-__device__ __forceinline__ float mppi_exp(float x) { return ::expf(x); }
-
 template <typename T>
 __device__ __forceinline__ T mppi_clamp(T a) { return a < T(-1) ? T(-1) : (a > T(1) ? T(1) : a); }
-
-// step 4: the total of the eight partials of robot t
-template <typename T>
-__device__ __forceinline__ T mppi_tree(const T* p, int t) {
-#pragma clang fp contract(off)
-  constexpr int E = kMppiRobots;
-  return ((p[0 * E + t] + p[1 * E + t]) + (p[2 * E + t] + p[3 * E + t])) + ((p[4 * E + t] + p[5 * E + t]) + (p[6 * E + t] + p[7 * E + t]));
-}
 
 template <typename T>
 __global__ __launch_bounds__(kMppiRobots * kMppiChunks) void mppi_update_kernel(const MppiArgs<T> P) {
 #pragma clang fp contract(off)
-  static_assert(kMppiChunks == 8, "mppi_tree is written for eight partials");
+  static_assert(kMppiChunks == kPartials && kMppiRobots == kPartialLanes, "the partials of os2r_partials.hpp");
   constexpr int E = kMppiRobots, C = kMppiChunks;
   __shared__ T sMax[C * E], sW[C * E], sQ[C * E], sA[4 * C * E];
   __shared__ int sCnt[C * E];
@@ -115,7 +95,7 @@ __global__ __launch_bounds__(kMppiRobots * kMppiChunks) void mppi_update_kernel(
     int cnt = 0;
     for (int s = c; s < S; s += C) {
       const T r = P.returns[(long long)s * M + m];
-      const bool ok = mppi_finite(r);
+      const bool ok = hi_finite(r);                     // (by its exponent bits: os2r_bits.hpp says why)
       const T rv = ok ? r : T(0);
       const bool take = ok && (cnt == 0 || rv > mx);
       mx = take ? rv : mx;
@@ -146,9 +126,9 @@ __global__ __launch_bounds__(kMppiRobots * kMppiChunks) void mppi_update_kernel(
       const long long lane = (long long)s * M + m;
       const T r = P.returns[lane];
       const MppiPair<T> a = src[lane];
-      const bool ok = mppi_finite(r);
+      const bool ok = hi_finite(r);
       const T rv = ok ? r : rmax;
-      const T e = mppi_exp((rv - rmax) * beta);
+      const T e = exp_of((rv - rmax) * beta);
       const T w = ok ? e : T(0);
       pw = pw + w;
       pq = pq + w * w;
@@ -171,12 +151,12 @@ __global__ __launch_bounds__(kMppiRobots * kMppiChunks) void mppi_update_kernel(
   __syncthreads();
 
   // steps 5 and 8: the value of slot k, the same in every wave
-  const T wsum = mppi_tree<T>(sW, t);
+  const T wsum = partials_tree<T>(sW, t);
   T out0 = T(0), out1 = T(0);
   if (!zeroed) {
     if (count > 0) {
-      out0 = mppi_clamp(mppi_tree<T>(sA + 0 * C * E, t) / wsum);
-      out1 = mppi_clamp(mppi_tree<T>(sA + 1 * C * E, t) / wsum);
+      out0 = mppi_clamp(partials_tree<T>(sA + 0 * C * E, t) / wsum);
+      out1 = mppi_clamp(partials_tree<T>(sA + 1 * C * E, t) / wsum);
     } else {
       out0 = P.nominal_in[((long long)ks * M + m) * 2];
       out1 = P.nominal_in[((long long)ks * M + m) * 2 + 1];
@@ -190,8 +170,8 @@ __global__ __launch_bounds__(kMppiRobots * kMppiChunks) void mppi_update_kernel(
       if (P.applied) {
         T ap0, ap1;
         if (count > 0) {
-          ap0 = mppi_clamp(mppi_tree<T>(sA + 2 * C * E, t) / wsum);
-          ap1 = mppi_clamp(mppi_tree<T>(sA + 3 * C * E, t) / wsum);
+          ap0 = mppi_clamp(partials_tree<T>(sA + 2 * C * E, t) / wsum);
+          ap1 = mppi_clamp(partials_tree<T>(sA + 3 * C * E, t) / wsum);
         } else {
           ap0 = P.nominal_in[m * 2];
           ap1 = P.nominal_in[m * 2 + 1];
@@ -200,7 +180,7 @@ __global__ __launch_bounds__(kMppiRobots * kMppiChunks) void mppi_update_kernel(
         P.applied[m * 2 + 1] = ap1;
       }
       if (P.ess) {
-        const T q = mppi_tree<T>(sQ, t);
+        const T q = partials_tree<T>(sQ, t);
         P.ess[m] = count > 0 ? (wsum * wsum) / q : T(0);
       }
       if (P.count) P.count[m] = count;

@@ -40,9 +40,7 @@
 // The arithmetic is the contract of include/os2r_pf.h: the layout's dtype, no contraction, each partial in ascending order.
 // tests/test_pf_host.py restates it in numpy; tests/test_gpu_pf.py compares bit for bit.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
+#include "os2r_partials.hpp"
 #include "../../include/os2r_pf.h"
 
 namespace os2r {
@@ -70,14 +68,8 @@ struct PfArgs {
   T ratio;                        // resample_ratio, rounded to T by the host
 };
 
-// The library is built with -fno-honor-nans -fno-honor-infinities: a log-weight is found finite or not by its exponent bits, and
-// the word that holds them passes through an empty asm as an integer (os2r_mppi.hpp says why hiding the floating-point value
-// alone is not enough).  For the same reason -infinity is never a floating-point constant here: it is stored as its bits.
-__device__ __forceinline__ unsigned pf_opaque_bits(unsigned b) { asm volatile("" : "+v"(b)); return b; }
-__device__ __forceinline__ bool pf_finite(double x) { return (pf_opaque_bits((unsigned)__double2hiint(x)) >> 20 & 0x7ffu) != 0x7ffu; }
-__device__ __forceinline__ bool pf_finite(float x) { return (pf_opaque_bits((unsigned)__float_as_int(x)) >> 23 & 0xffu) != 0xffu; }
-__device__ __forceinline__ double pf_exp(double x) { return ::exp(x); }
-__device__ __forceinline__ float pf_exp(float x) { return ::expf(x); }
+// A log-weight is found finite or not by its exponent bits (hi_finite: os2r_bits.hpp says why).  For the same reason -infinity is
+// never a floating-point constant here: it is stored as its bits.
 typedef long long __attribute__((may_alias)) pf_bits64;
 typedef int __attribute__((may_alias)) pf_bits32;
 // *p = ok ? x : -infinity, the choice made on the bits
@@ -86,14 +78,6 @@ __device__ __forceinline__ void pf_store_or_minus_inf(double* p, bool ok, double
 }
 __device__ __forceinline__ void pf_store_or_minus_inf(float* p, bool ok, float x) {
   *(pf_bits32*)p = ok ? __float_as_int(x) : (int)0xff800000u;
-}
-
-// step 6: the total of the eight partials of robot t
-template <typename T>
-__device__ __forceinline__ T pf_tree(const T* p, int t) {
-#pragma clang fp contract(off)
-  constexpr int E = kPfRobots;
-  return ((p[0 * E + t] + p[1 * E + t]) + (p[2 * E + t] + p[3 * E + t])) + ((p[4 * E + t] + p[5 * E + t]) + (p[6 * E + t] + p[7 * E + t]));
 }
 
 // steps 1 and 2 for one lane: its observation into o, -> l.  pr, the precisions, are in LDS and read there for every particle, at
@@ -129,7 +113,7 @@ __device__ __forceinline__ T pf_log_weight(const PfArgs<T>& P, long long lane, c
 template <typename T>
 __global__ __launch_bounds__(kPfRobots * kPfChunks) void pf_update_kernel(const PfArgs<T> P) {
 #pragma clang fp contract(off)
-  static_assert(kPfChunks == 8, "pf_tree is written for eight partials");
+  static_assert(kPfChunks == kPartials && kPfRobots == kPartialLanes, "the partials of os2r_partials.hpp");
   constexpr int E = kPfRobots, C = kPfChunks;
   __shared__ T sMax[C * E], sW[C * E], sQ[C * E], sE[kPfObs * C * E];
   __shared__ T sPrec[kPfObs];
@@ -157,7 +141,7 @@ __global__ __launch_bounds__(kPfRobots * kPfChunks) void pf_update_kernel(const 
     int cnt = 0;
     for (int s = c; s < S; s += C) {
       const T l = pf_log_weight<T>(P, (long long)s * M + m, y, pr, o);
-      const bool ok = pf_finite(l);
+      const bool ok = hi_finite(l);
       const T lv = ok ? l : T(0);
       const bool take = ok && (cnt == 0 || lv > mx);
       mx = take ? lv : mx;
@@ -187,10 +171,10 @@ __global__ __launch_bounds__(kPfRobots * kPfChunks) void pf_update_kernel(const 
     for (int s = c; s < S; s += C) {
       const long long lane = (long long)s * M + m;
       const T l = pf_log_weight<T>(P, lane, y, pr, o);
-      const bool ok = pf_finite(l);
+      const bool ok = hi_finite(l);
       const T lv = ok ? l : lmax;
       const T arg = lv - lmax;
-      const T e = pf_exp(arg);
+      const T e = exp_of(arg);
       const T w = ok ? e : T(0);
       pw = pw + w;
       pq = pq + w * w;
@@ -215,14 +199,14 @@ __global__ __launch_bounds__(kPfRobots * kPfChunks) void pf_update_kernel(const 
   __syncthreads();
 
   // steps 7 and 9, the same in every wave
-  const T wsum = pf_tree<T>(sW, t);
-  const T ess = lost ? T(0) : (wsum * wsum) / pf_tree<T>(sQ, t);
+  const T wsum = partials_tree<T>(sW, t);
+  const T ess = lost ? T(0) : (wsum * wsum) / partials_tree<T>(sQ, t);
   const bool res = !lost && (ess < P.ratio * T(S) || count < S);
   const bool any_res = __builtin_amdgcn_ballot_w64(res) != 0;     // every wave holds the same 64 robots: uniform over the workgroup
 
   if (c == 0 && valid) {
     if (want_est)                                                   // step 8
-      for (int i = 0; i < D; ++i) P.est[m * D + i] = lost ? P.meas[m * D + i] : pf_tree<T>(sE + i * C * E, t) / wsum;
+      for (int i = 0; i < D; ++i) P.est[m * D + i] = lost ? P.meas[m * D + i] : partials_tree<T>(sE + i * C * E, t) / wsum;
     if (P.ess) P.ess[m] = ess;
     if (P.count) P.count[m] = count;
     if (P.resampled) P.resampled[m] = res ? 1 : 0;
@@ -235,8 +219,8 @@ __global__ __launch_bounds__(kPfRobots * kPfChunks) void pf_update_kernel(const 
   if (valid && res) {
     T* const lw = P.logw_out + m;
     auto to_weight = [](T a) {
-      const bool ok = pf_finite(a);
-      const T e = pf_exp(ok ? a : T(0));
+      const bool ok = hi_finite(a);
+      const T e = exp_of(ok ? a : T(0));
       return ok ? e : T(0);
     };
     int s = c;
@@ -278,7 +262,7 @@ __global__ __launch_bounds__(kPfRobots * kPfChunks) void pf_update_kernel(const 
     const T step = sW[t], inv = T(1) / step;
     const int last = sCnt[t];
     T u = P.u ? P.u[m] : T(0.5);
-    u = pf_finite(u) && u >= T(0) && u < T(1) ? u : T(0.5);
+    u = hi_finite(u) && u >= T(0) && u < T(1) ? u : T(0.5);
     // k(x): the number of slots n < S with t_n < x
     auto slots_below = [&](T x) {
       const T guess = x * inv - u;

@@ -17,9 +17,13 @@
 // register array at run time, nothing goes to scratch (tests/test_ilqr_steer_host.py reads the metadata).
 //
 // The arithmetic is the contract of include/os2r_steer.h.  tests/test_ilqr_steer_host.py restates it in numpy, bit for bit.
+//
+// The knot loop, the scan and the write-back below are still a copy of os2r_search.hpp's text, against the rule of DESIGN.md
+// section 4: split into three functions that both kernels call, the fp64 line search measured 3 to 13 % slower
+// (profiles/refactor_bodies_ab.txt).  Whoever changes one of the two texts changes the other.
 #pragma once
 #include "os2r_search.hpp"
-#include "os2r_ilqr_mu.hpp"   // steer_bits and the class tests made of them
+#include "os2r_bits.hpp"   // steer_finite, steer_nan, steer_invalid, steer_abs
 #include "../../include/os2r_steer.h"
 
 namespace os2r {
@@ -34,9 +38,6 @@ struct SteerArgs {
   T armijo, shrink, grow, mu_floor, mu_start, mu_max, tol;   // the rule, rounded to T by the host
   T alpha[OS2RC_MAX_ALPHAS];           // rounded to T by the host
 };
-
-__device__ __forceinline__ double steer_abs(double x) { return __longlong_as_double(__double_as_longlong(x) & 0x7fffffffffffffffll); }
-__device__ __forceinline__ float steer_abs(float x) { return __int_as_float(__float_as_int(x) & 0x7fffffff); }
 
 template <typename T, int NQ>
 __global__ __launch_bounds__(kSearchTraj * OS2RC_MAX_ALPHAS) void ilqr_steer_kernel(const SteerArgs<T> S) {

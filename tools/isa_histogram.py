@@ -56,6 +56,34 @@ def classify(mn):
     return "other"
 
 
+def instructions(dis):
+    """[(address, mnemonic, operands)] of the instruction lines in a piece of llvm-objdump -d --no-show-raw-insn output"""
+    insts = []
+    for ln in dis.splitlines():
+        m = re.match(r"^\s+(\S+)\s+(.*?)\s*//\s*([0-9A-Fa-f]+):", ln)
+        if m:
+            insts.append((int(m.group(3), 16), m.group(1), m.group(2)))
+    return insts
+
+
+def disassemble_all(path):
+    """-> {demangled name: [(address, mnemonic, operands)]} of every function of every gfx950 code object in `path`"""
+    out = {}
+    for co in code_objects(path):
+        with tempfile.NamedTemporaryFile(suffix=".co") as f:
+            f.write(co)
+            f.flush()
+            syms = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "-sW", f.name], capture_output=True, text=True).stdout
+            names = [ln.split()[7] for ln in syms.splitlines() if " FUNC " in ln]
+            dis = subprocess.run([os.path.join(LLVM, "llvm-objdump"), "-d", "--no-show-raw-insn", f.name], capture_output=True, text=True).stdout
+        plain = dict(zip(names, demangle(names)))
+        for part in re.split(r"^(?=[0-9A-Fa-f]+ <\S+>:$)", dis, flags=re.M):
+            m = re.match(r"[0-9A-Fa-f]+ <(\S+)>:", part)
+            if m and m.group(1) in plain:
+                out[plain[m.group(1)].strip()] = instructions(part)
+    return out
+
+
 def disassemble(path, needle, counting=False):
     """-> (demangled name, [(address, mnemonic, operands)]) of the first kernel whose name contains `needle`"""
     for co in code_objects(path):
@@ -73,12 +101,7 @@ def disassemble(path, needle, counting=False):
                 if needle in dn and is_counting == counting and (not is_rollout or "true>(" in needle):
                     dis = subprocess.run([os.path.join(LLVM, "llvm-objdump"), "-d", "--no-show-raw-insn", f"--disassemble-symbols={x[7]}", f.name],
                                          capture_output=True, text=True).stdout
-                    insts = []
-                    for ln in dis.splitlines():
-                        m = re.match(r"^\s+(\S+)\s+(.*?)\s*//\s*([0-9A-Fa-f]+):", ln)
-                        if m:
-                            insts.append((int(m.group(3), 16), m.group(1), m.group(2)))
-                    return dn, int(x[2]), insts
+                    return dn, int(x[2]), instructions(dis)
     raise SystemExit(f"no kernel containing {needle!r} in {path}")
 
 
