@@ -77,10 +77,19 @@ class Os2rLibraryMissing(ImportError):
     pass
 
 
+class Os2rError(RuntimeError):
+    """A call of one of the libraries returned a status that is not OK (gym_os2r_amd.sim re-exports it)."""
+
+
+def _ptr(t):
+    """A tensor (or None) as the pointer argument of a C call."""
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
 def load_library(path, entry_points, last_error, version, missing, build_hint, mismatch):
     """One C-ABI library through ctypes: argument and result types from its table of entry points (the result is c_int, c_char_p
     for `last_error`), the ABI number `version` = (symbol, expected) checked.  A file that is not there raises
-    missing(f"{path} not found: {build_hint}"), another ABI ImportError(mismatch).  The four loaders keep what this returns."""
+    missing(f"{path} not found: {build_hint}"), another ABI ImportError(mismatch).  The loaders keep what this returns."""
     if not os.path.exists(path):
         raise missing(f"{path} not found: {build_hint}")
     # torch first: the library needs libamdhip64, and the process must hold ONE HIP runtime -- the one torch brings.  Loaded before
@@ -96,6 +105,20 @@ def load_library(path, entry_points, last_error, version, missing, build_hint, m
     if getattr(lib, symbol)() != expected:
         raise ImportError(mismatch)
     return lib
+
+
+def companion(scope, name, prefix, env_var, missing):
+    """(LIB_PATH, load) of the loader module whose globals() are `scope`, for the companion library lib`name`.so whose symbols start
+    with `prefix`: the path is `env_var` or next to this file; load(), at its first call, reads the module's LIB_PATH, ENTRY_POINTS
+    and ABI_VERSION and keeps the library as the module's _lib."""
+    def load():
+        if scope.get("_lib") is None:
+            scope["_lib"] = load_library(scope["LIB_PATH"], scope["ENTRY_POINTS"], f"{prefix}_last_error",
+                                         (f"{prefix}_abi_version", scope["ABI_VERSION"]), missing,
+                                         "build the HIP extension first (make -C gym-os2r_amd/csrc). There is no CPU fallback.",
+                                         f"lib{name}.so ABI version does not match {scope['__name__']}")
+        return scope["_lib"]
+    return os.environ.get(env_var) or os.path.join(_HERE, f"lib{name}.so"), load
 
 
 def load_record():

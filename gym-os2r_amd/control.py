@@ -8,14 +8,9 @@ library has not been built (``make -C gym-os2r_amd/csrc``), load() raises.
 from __future__ import annotations
 
 import ctypes as C
-import os
 
 from . import abi
-from ._lib import load_library
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("OS2R_CONTROL_LIBRARY") or os.path.join(_HERE, "libos2r_control.so")
-_lib = None
+from ._lib import companion as _companion
 
 ABI_VERSION = 1          # OS2R_CONTROL_ABI_VERSION
 MAX_ALPHAS = 16          # OS2RC_MAX_ALPHAS
@@ -45,13 +40,8 @@ class Os2rControlLibraryMissing(ImportError):
     pass
 
 
-def load():
-    global _lib
-    if _lib is None:
-        _lib = load_library(LIB_PATH, ENTRY_POINTS, "os2rc_last_error", ("os2rc_abi_version", ABI_VERSION), Os2rControlLibraryMissing,
-                            "build the HIP extension first (make -C gym-os2r_amd/csrc). There is no CPU fallback.",
-                            "libos2r_control.so ABI version does not match gym_os2r_amd.control")
-    return _lib
+# the library through ctypes, loaded once; OS2R_CONTROL_LIBRARY: A/B builds of the same ABI
+LIB_PATH, load = _companion(globals(), "os2r_control", "os2rc", "OS2R_CONTROL_LIBRARY", Os2rControlLibraryMissing)
 
 
 def slot_columns(task, nq):

@@ -1,0 +1,621 @@
+"""The controller calls of a HipSim: LQR gains, the iLQR backward pass, its line search with and without a steered mu, the MPPI
+update and the particle-filter update, each as an allocation-free ``*_into`` on tensors in the kernel's layout and an allocating
+wrapper around it.  ``Controllers`` is the plain base class HipSim (gym_os2r_amd.sim) inherits them from; it uses the handle's
+``_out``, ``_in``, ``_new``, ``_layout``, ``_stream`` and ``_check``.
+
+Every check runs before a library is loaded or called.  What several methods check is written once, in the functions below;
+the shape tables stay with their method.  A wrapper repeats a check of its ``*_into`` only where it has to run before the
+wrapper permutes, copies or allocates.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+
+import torch
+
+from . import abi, control, mppi, pf, search, steer
+from ._lib import Os2rError, _ptr
+
+NOMINAL_KEYS = ("cost", "actions", "obs", "end_obs", "lx", "lu", "p_final")
+
+
+def _call(module, entry, last_error, *args):
+    """Entry point `entry` of the companion library `module` loads; a status that is not OK raises Os2rError with the library's text."""
+    lib = module.load()
+    rc = getattr(lib, entry)(*args)
+    if rc != abi.OK:
+        raise Os2rError(f"{entry} failed ({rc}): {getattr(lib, last_error)().decode()}")
+
+
+def _split(what, lanes, per, of, unit, ok=True):
+    """The `lanes` lanes of `of`, `per` of them (the argument `unit`) to each trajectory or robot -> how many of those there are."""
+    if not ok or lanes < per or lanes % per:
+        raise ValueError(f"{what}: the {lanes} lanes of {of} are no multiple of {unit} = {per}")
+    return lanes // per
+
+
+def _count(what, name, v):
+    """`v` is an integer >= 1 and no bool."""
+    if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+        raise ValueError(f"{what}: {name} must be an integer >= 1, got {v!r}")
+    return v
+
+
+def _finite(what, name, v, ok, must, shown=None):
+    """float(v), finite and ok(it) -- the error says "finite and `must`" and shows the float, or `shown`."""
+    try:
+        x = float(v)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: {name} must be a number, got {type(v)}") from None
+    if not math.isfinite(x) or not ok(x):
+        raise ValueError(f"{what}: {name} must be finite and {must}, got {x if shown is None else shown}")
+    return x
+
+
+def _not_negative(x):
+    return x >= 0.0
+
+
+def _invertible(x):
+    return x > 0.0 and math.isfinite(1.0 / x)
+
+
+def _nominal_dict(what, nominal, wanted):
+    """`nominal` is a dict with every entry a line search keeps."""
+    if not isinstance(nominal, dict) or any(k not in nominal for k in NOMINAL_KEYS):
+        raise ValueError(f"{what}: nominal must be {wanted} returned")
+
+
+class Controllers:
+    """The controller methods of HipSim."""
+
+    def _outs(self, what, rows):
+        """self._out for every row (tensor, shape, dtype or None: the handle's, name), the errors naming the method `what`."""
+        for t, shape, dtype, name in rows:
+            self._out(t, shape, dtype or self.dtype, f"{what}: {name}")
+
+    def _other_buffer(self, kept, shape, t):
+        """Of the two buffers of `shape` the handle keeps in its dict `kept`, made at the first call: the one `t` (a tensor or None) is not."""
+        pairs = self.__dict__.setdefault(kept, {})
+        if shape not in pairs:
+            pairs[shape] = (self._new(*shape), self._new(*shape))
+        first, second = pairs[shape]
+        return first if t is None or t.data_ptr() != first.data_ptr() else second
+
+    # -- LQR gains --------------------------------------------------------------------------
+    def _lqr_cost(self, Q, R, what="lqr_gains"):
+        """Q [2nq, 2nq] and R [2, 2] of lqr_gains() -> two ctypes double arrays (row-major), checked: host values, finite and
+        exactly symmetric (include/os2r.h: os2r_lqr_gains).  `what`: the method the errors name."""
+        n = 2 * self.nq
+        out = []
+        for name, m, k in (("Q", Q, n), ("R", R, 2)):
+            try:
+                if isinstance(m, torch.Tensor):
+                    t = m.detach().to("cpu", torch.float64)
+                else:                              # (through numpy: torch would make float32 of a list of Python floats)
+                    import numpy as np
+                    t = torch.from_numpy(np.array(m, dtype=np.float64))
+            except (TypeError, ValueError, RuntimeError):
+                raise ValueError(f"{what}: {name} must be a [{k}, {k}] array of numbers, got {type(m)}") from None
+            if tuple(t.shape) != (k, k):
+                raise ValueError(f"{what}: {name} must have shape ({k}, {k}), got {tuple(t.shape)}")
+            if not bool(torch.isfinite(t).all()):
+                raise ValueError(f"{what}: {name} must be finite")
+            if not bool((t == t.T).all()):
+                raise ValueError(f"{what}: {name} must be exactly symmetric")
+            out.append((C.c_double * (k * k))(*t.reshape(-1).tolist()))
+        return out
+
+    def _riccati_lanes(self, what, A, K):
+        """A [2nq, 2nq, L] of lqr_gains_into / ilqr_backward_into -> (L, M = L / K)."""
+        n = 2 * self.nq
+        if not isinstance(A, torch.Tensor) or A.dim() != 3:
+            raise ValueError(f"{what}: A must be a tensor of shape ({n}, {n}, knots * M)")
+        L = int(A.shape[2])
+        return L, _split(what, L, K, "A", "knots")
+
+    def _riccati_views(self, what, A, B, K):
+        """A [L, 2nq, 2nq] and B [L, 2nq, 2] of lqr_gains / ilqr_backward -> (a, b, L, M = L / K), a and b in the kernel's layout."""
+        n = 2 * self.nq
+        for name, t, w in (("A", A, n), ("B", B, 2)):
+            if not isinstance(t, torch.Tensor) or t.dim() != 3 or tuple(t.shape[1:]) != (n, w):
+                raise ValueError(f"{what}: {name} must be a tensor of shape (knots * M, {n}, {w}), got "
+                                 f"{tuple(getattr(t, 'shape', ())) or type(t)}")
+            if t.dtype != self.dtype or t.device != self.device:
+                raise ValueError(f"{what}: {name} must be {self.dtype} on {self.device}, got {t.dtype} on {t.device}")
+        L = int(A.shape[0])
+        if int(B.shape[0]) != L:
+            raise ValueError(f"{what}: A has {L} lanes, B {int(B.shape[0])}")
+        M = _split(what, L, K, "A", "knots")
+        return A.permute(1, 2, 0).contiguous(), B.permute(1, 2, 0).contiguous(), L, M     # no copy for what linearize() returned
+
+    def lqr_gains_into(self, A, B, Q, R, *, knots: int = 1, sweeps: int = 1, P_final=None, gains_out=None, P_out=None, flags_out=None,
+                       actions=None, obs=None, weights_out=None):
+        """Allocation-free variant of lqr_gains() on tensors in the kernel's layout (include/os2r.h: os2r_lqr_gains), the
+        trajectory index fastest: with K = knots, L = K M and n = 2nq, A [n, n, L], B [n, 2, L], P_final [n, n, M] or None (Q),
+        gains_out [K, 2, n, M], P_out [n, n, M] (may be P_final), flags_out [K, M] uint8, weights_out [K, 2, D+1, M] with
+        actions [L, 2] and obs [L, D]; each output may be None, not all of gains_out, P_out and weights_out.  Shapes, dtypes,
+        device and contiguity are checked before the library is called (it takes addresses)."""
+        what = "lqr_gains"
+        n = 2 * self.nq
+        K, sweeps = int(knots), int(sweeps)
+        if K < 1 or sweeps < 1:
+            raise ValueError(f"{what}: knots and sweeps must be >= 1, got {K} and {sweeps}")
+        q, r = self._lqr_cost(Q, R)
+        L, M = self._riccati_lanes(what, A, K)
+        if gains_out is None and P_out is None and weights_out is None:
+            raise ValueError(f"{what}: nothing asked for (gains, P and weights are all off)")
+        if weights_out is not None and (actions is None or obs is None):
+            raise ValueError(f"{what}: weights need actions and obs (the point each knot was linearised about)")
+        if weights_out is None:
+            actions = obs = None
+        self._outs(what, ((A, (n, n, L), None, "A"), (B, (n, 2, L), None, "B"), (P_final, (n, n, M), None, "P_final"),
+                          (gains_out, (K, 2, n, M), None, "gains_out"), (P_out, (n, n, M), None, "P_out"),
+                          (flags_out, (K, M), torch.uint8, "flags_out"), (weights_out, (K, 2, self.D + 1, M), None, "weights_out"),
+                          (actions, (L, 2), None, "actions"), (obs, (L, self.D), None, "obs")))
+        if B is None:
+            raise ValueError(f"{what}: B is required")
+        self._check(self._lib.os2r_lqr_gains(self._h, K, M, sweeps, _ptr(A), _ptr(B), q, r, _ptr(P_final), _ptr(gains_out), _ptr(P_out),
+                                             _ptr(flags_out), _ptr(actions), _ptr(obs), _ptr(weights_out), self._stream()), "os2r_lqr_gains")
+
+    def lqr_gains(self, A, B, Q, R, *, knots: int = 1, sweeps: int = 1, P_final=None, actions=None, obs=None, want_gains: bool = True,
+                  want_P: bool = False, want_flags: bool = True, want_weights: bool = False):
+        """The backward Riccati recursion of L = knots * M independent LQR problems in one launch (include/os2r.h:
+        os2r_lqr_gains; the arithmetic and its order are spelled out there).  A [L, 2nq, 2nq] and B [L, 2nq, 2] as linearize()
+        returns them -- permuted views of the kernel's layout are taken without a copy, anything else is copied once --, lane
+        k * M + m is knot k of trajectory m (a knot handle filled knot-major by copy_envs).  Q [2nq, 2nq] and R [2, 2]: host
+        values, finite, exactly symmetric.  P_final [M, 2nq, 2nq] or None (Q): the cost-to-go behind the last knot.  The knots
+        are passed `sweeps` times from the last to the first, P carried across: knots=1 with many sweeps is the stationary
+        iteration, several knots with several sweeps the periodic one of a wrapped schedule.
+        -> (gains [K, M, 2, 2nq], P [M, 2nq, 2nq], flags [K, M] uint8, weights [M, K, 2, D+1]), None where not wanted; all are
+        permuted views of the kernel's layouts.  flags is 1 where a knot's 2 x 2 system R + B'PB was refused (not positive
+        definite, or not finite): that knot's gain is 0.  weights (needs actions [L, 2] and obs [L, D], the point each knot was
+        linearised about) is the per-environment table rollout_schedule takes for a handle of M environments, holding
+        a = a0 - K_k (x - x_k) on the raw observation slots; rollout_schedule's .contiguous() on it is a no-op."""
+        what = "lqr_gains"
+        n = 2 * self.nq
+        K = int(knots)
+        if K < 1 or int(sweeps) < 1:                  # (here too: the lanes are split by K below)
+            raise ValueError(f"{what}: knots and sweeps must be >= 1, got {K} and {int(sweeps)}")
+        if want_weights and (actions is None or obs is None):       # (here too: _in would make a tensor of None)
+            raise ValueError(f"{what}: weights need actions and obs (the point each knot was linearised about)")
+        a, b, L, M = self._riccati_views(what, A, B, K)
+        pfin = None
+        if P_final is not None:
+            pfin = self._in(P_final, (M, n, n)).permute(1, 2, 0).contiguous()
+        act = ob = None
+        if want_weights:
+            act, ob = self._in(actions, (L, 2)), self._in(obs, (L, self.D))
+        gains = self._new(K, 2, n, M) if want_gains else None
+        pout = self._new(n, n, M) if want_P else None
+        flags = self._new(K, M, dtype=torch.uint8) if want_flags else None
+        wts = self._new(K, 2, self.D + 1, M) if want_weights else None
+        self.lqr_gains_into(a, b, Q, R, knots=K, sweeps=sweeps, P_final=pfin, gains_out=gains, P_out=pout, flags_out=flags, actions=act,
+                            obs=ob, weights_out=wts)
+        return (gains.permute(0, 3, 1, 2) if want_gains else None, pout.permute(2, 0, 1) if want_P else None, flags,
+                wts.permute(3, 0, 1, 2) if want_weights else None)
+
+    # -- iLQR backward pass -----------------------------------------------------------------
+    def _ilqr_scalars(self, mu, alphas, want_weights, what="ilqr_backward"):
+        """mu and alphas of ilqr_backward() (the alphas of ilqr_steer()) -> (float, ctypes double array or None), checked.
+        `what`: the method the errors name."""
+        mu = _finite(what, "mu", mu, _not_negative, ">= 0")
+        if not want_weights:
+            return mu, None
+        try:
+            al = [float(v) for v in (alphas.tolist() if hasattr(alphas, "tolist") else alphas)]
+        except (TypeError, ValueError):
+            raise ValueError(f"{what}: alphas must be a sequence of numbers, got {type(alphas)}") from None
+        if not 1 <= len(al) <= 16:
+            raise ValueError(f"{what}: between 1 and 16 alphas, got {len(al)}")
+        if not all(math.isfinite(v) for v in al):
+            raise ValueError(f"{what}: every alpha must be finite, got {al}")
+        return mu, (C.c_double * len(al))(*al)
+
+    def ilqr_backward_into(self, A, B, Q, R, *, knots: int = 1, lx=None, lu=None, mu: float = 0.0, P_final=None, p_final=None,
+                           gains_out=None, ff_out=None, P_out=None, p_out=None, flags_out=None, dv_out=None, actions=None, obs=None,
+                           alphas=None, weights_out=None, mu_dev=None):
+        """Allocation-free variant of ilqr_backward() on tensors in the kernel's layout (include/os2r_control.h:
+        os2rc_ilqr_backward), the trajectory index fastest: with K = knots, L = K M and n = 2nq, A [n, n, L], B [n, 2, L],
+        lx [n, L], lu [2, L], P_final [n, n, M], p_final [n, M] (each of the four None for its default), gains_out [K, 2, n, M],
+        ff_out [K, 2, M], P_out [n, n, M] (may be P_final), p_out [n, M] (may be p_final), flags_out [K, M] uint8,
+        dv_out [K, 2, M], weights_out [K, 2, D+1, len(alphas) M] with actions [L, 2], obs [L, D] and alphas; each output may be
+        None, not all of them but flags_out.  mu_dev [M]: one mu per trajectory, read on the device (include/os2r_steer.h:
+        os2rt_ilqr_backward_mu; mu itself must then be 0).  Shapes, dtypes, device and contiguity are checked before the library is
+        called (it takes addresses)."""
+        what = "ilqr_backward"
+        n = 2 * self.nq
+        K = int(knots)
+        if K < 1:
+            raise ValueError(f"{what}: knots must be >= 1, got {K}")
+        q, r = self._lqr_cost(Q, R, what)
+        L, M = self._riccati_lanes(what, A, K)
+        if all(t is None for t in (gains_out, ff_out, P_out, p_out, dv_out, weights_out)):
+            raise ValueError(f"{what}: nothing asked for (gains, ff, P, p, dv and weights are all off)")
+        if weights_out is not None and (actions is None or obs is None or alphas is None):
+            raise ValueError(f"{what}: weights need actions, obs (the point each knot was linearised about) and alphas")
+        mu, al = self._ilqr_scalars(mu, alphas, weights_out is not None)
+        if mu_dev is not None and mu != 0.0:
+            raise ValueError(f"{what}: mu_dev and a nonzero mu ({mu}) are both given; the regularisation is one or the other")
+        self._out(mu_dev, (M,), self.dtype, f"{what}: mu_dev")
+        if B is None:
+            raise ValueError(f"{what}: B is required")
+        nal = 0 if al is None else len(al)
+        if weights_out is None:
+            actions = obs = None
+        self._outs(what, ((A, (n, n, L), None, "A"), (B, (n, 2, L), None, "B"), (lx, (n, L), None, "lx"), (lu, (2, L), None, "lu"),
+                          (P_final, (n, n, M), None, "P_final"), (p_final, (n, M), None, "p_final"),
+                          (gains_out, (K, 2, n, M), None, "gains_out"), (ff_out, (K, 2, M), None, "ff_out"), (P_out, (n, n, M), None, "P_out"),
+                          (p_out, (n, M), None, "p_out"), (dv_out, (K, 2, M), None, "dv_out"), (flags_out, (K, M), torch.uint8, "flags_out"),
+                          (weights_out, (K, 2, self.D + 1, nal * M), None, "weights_out"), (actions, (L, 2), None, "actions"),
+                          (obs, (L, self.D), None, "obs")))
+        # the two entry points differ in the regularisation alone: a host value, or one per trajectory read on the device
+        head = (C.byref(self._layout()), K, M, _ptr(A), _ptr(B), _ptr(lx), _ptr(lu), q, r)
+        tail = (_ptr(P_final), _ptr(p_final), _ptr(gains_out), _ptr(ff_out), _ptr(P_out), _ptr(p_out), _ptr(flags_out), _ptr(dv_out),
+                _ptr(actions), _ptr(obs), al, nal, _ptr(weights_out), self._stream())
+        if mu_dev is None:
+            _call(control, "os2rc_ilqr_backward", "os2rc_last_error", *head, mu, *tail)
+        else:
+            _call(steer, "os2rt_ilqr_backward_mu", "os2rt_last_error", *head, _ptr(mu_dev), *tail)
+
+    def ilqr_backward(self, A, B, Q, R, *, knots, lx=None, lu=None, mu=0.0, P_final=None, p_final=None, actions=None, obs=None,
+                      alphas=None, want_gains=True, want_ff=True, want_P=False, want_p=False, want_flags=True, want_dv=True,
+                      want_weights=False, mu_dev=None):
+        """The backward pass of iLQR for M = L / knots independent trajectories in one launch (include/os2r_control.h:
+        os2rc_ilqr_backward; the arithmetic and its order are spelled out there): lqr_gains(sweeps=1) with its affine terms.
+        A [L, 2nq, 2nq] and B [L, 2nq, 2] as linearize() returns them (taken without a copy), lane k * M + m knot k of trajectory
+        m; lx [L, 2nq] and lu [L, 2] the cost gradients at the knots (None: zeros); Q, R the cost Hessians as in lqr_gains;
+        mu >= 0 the control-space regularisation; P_final [M, 2nq, 2nq] (None: Q) and p_final [M, 2nq] (None: zeros) the value
+        function behind the last knot.
+        -> (gains [K, M, 2, 2nq], ff [K, M, 2], P [M, 2nq, 2nq], p [M, 2nq], flags [K, M] uint8, dv [K, M, 2],
+        weights [len(alphas) M, K, 2, D+1]), None where not wanted; all are permuted views of the kernel's layouts.  The control
+        law of knot k is a = a_k + alpha ff_k - gains_k (x - x_k); flags is 1 where a knot's regularised 2 x 2 system was refused
+        (gains and ff are 0 there); alpha dv[..., 0].sum(0) + alpha^2 dv[..., 1].sum(0) is the model's cost change under step size
+        alpha.  weights (needs actions [L, 2], obs [L, D] and alphas) is the per-environment table rollout_schedule takes for a
+        handle of len(alphas) M environments, environment i M + m being trajectory m under alphas[i].
+        mu_dev [M] (the handle's dtype, on its device, contiguous; mu must then be 0): one mu per trajectory, read on the device
+        -- the array ilqr_steer keeps up to date.  Trajectory m gets what mu = mu_dev[m] gives it, bit for bit; a negative or
+        non-finite entry runs as 0 with every knot of that trajectory refused (include/os2r_steer.h: os2rt_ilqr_backward_mu)."""
+        what = "ilqr_backward"
+        n = 2 * self.nq
+        K = int(knots)
+        if K < 1:                                     # (here too: the lanes are split by K below)
+            raise ValueError(f"{what}: knots must be >= 1, got {K}")
+        if want_weights and (actions is None or obs is None or alphas is None):      # (here too: the table is sized by the alphas)
+            raise ValueError(f"{what}: weights need actions, obs (the point each knot was linearised about) and alphas")
+        al = self._ilqr_scalars(mu, alphas, want_weights)[1]
+        a, b, L, M = self._riccati_views(what, A, B, K)
+
+        def given(t, shape, name, perm):
+            if t is None:
+                return None
+            if (isinstance(t, torch.Tensor) and t.dtype == self.dtype and t.device == self.device and tuple(t.shape) == tuple(shape)
+                    and t.permute(*perm).is_contiguous()):
+                return t.permute(*perm)          # a permuted view of the kernel's layout (ilqr_line_search's *_view): no copy
+            try:
+                return self._in(t, shape).permute(*perm).contiguous()
+            except ValueError as e:
+                raise ValueError(f"{what}: {name}: {e}") from None
+        gx, gu = given(lx, (L, n), "lx", (1, 0)), given(lu, (L, 2), "lu", (1, 0))
+        pfin, vf = given(P_final, (M, n, n), "P_final", (1, 2, 0)), given(p_final, (M, n), "p_final", (1, 0))
+        act = ob = None
+        nal = 0
+        if want_weights:
+            nal = len(al)
+            act, ob = given(actions, (L, 2), "actions", (0, 1)), given(obs, (L, self.D), "obs", (0, 1))
+        gains = self._new(K, 2, n, M) if want_gains else None
+        ff = self._new(K, 2, M) if want_ff else None
+        pout = self._new(n, n, M) if want_P else None
+        vout = self._new(n, M) if want_p else None
+        flags = self._new(K, M, dtype=torch.uint8) if want_flags else None
+        dv = self._new(K, 2, M) if want_dv else None
+        wts = self._new(K, 2, self.D + 1, nal * M) if want_weights else None
+        self.ilqr_backward_into(a, b, Q, R, knots=K, lx=gx, lu=gu, mu=mu, P_final=pfin, p_final=vf, gains_out=gains, ff_out=ff, P_out=pout,
+                                p_out=vout, flags_out=flags, dv_out=dv, actions=act, obs=ob, alphas=alphas, weights_out=wts, mu_dev=mu_dev)
+        return (gains.permute(0, 3, 1, 2) if want_gains else None, ff.permute(0, 2, 1) if want_ff else None,
+                pout.permute(2, 0, 1) if want_P else None, vout.permute(1, 0) if want_p else None, flags,
+                dv.permute(0, 2, 1) if want_dv else None, wts.permute(3, 0, 1, 2) if want_weights else None)
+
+    # -- iLQR line search, plain and steering mu ----------------------------------------------
+    def _search_cost(self, what, Q, R, Q_final):
+        """Q, R and Q_final (or None) of a line search -> three ctypes double arrays (qf None for None), checked as _lqr_cost checks."""
+        q, r = self._lqr_cost(Q, R, what)
+        return q, r, None if Q_final is None else self._lqr_cost(Q_final, R, f"{what}: Q_final")[0]
+
+    def _search_geometry(self, what, target, knot_obs, one_refusal=False):
+        """target [M, D] and knot_obs [K, nalpha M, D] of a line search -> (M, K, N = nalpha M, nalpha, L = K M), checked;
+        `one_refusal`: the allocating forms' wording, one message for the ranks of both."""
+        D = self.D
+        no_target = not isinstance(target, torch.Tensor) or target.dim() != 2
+        no_knots = not isinstance(knot_obs, torch.Tensor) or knot_obs.dim() != 3
+        if one_refusal and (no_target or no_knots):
+            raise ValueError(f"{what}: target must be a tensor of shape (M, {D}) and knot_obs one of shape (K, nalpha * M, {D})")
+        if no_target:
+            raise ValueError(f"{what}: target must be a tensor of shape (M, {D})")
+        if no_knots:
+            raise ValueError(f"{what}: knot_obs must be a tensor of shape (K, nalpha * M, {D})")
+        M, K, N = int(target.shape[0]), int(knot_obs.shape[0]), int(knot_obs.shape[1])
+        if M < 1 or K < 1 or N < M or N % M:
+            raise ValueError(f"{what}: the {N} candidate lanes of knot_obs [{K} knots] are no multiple of the {M} trajectories of target")
+        nal = N // M
+        if not 1 <= nal <= 16:
+            raise ValueError(f"{what}: between 1 and 16 candidates per trajectory, got {nal}")
+        if K * N > 2 ** 31 - 1:
+            raise ValueError(f"{what}: {K} knots of {N} candidate lanes exceed what an int32 index addresses")
+        return M, K, N, nal, K * M
+
+    def _search_rows(self, geometry, knot_obs, end_obs, actions, done, target, cost, act_nom, obs_nom, end_nom, lx, lu, p_final, choice,
+                     index, cand_cost):
+        """The shape table both line searches share, as a list: ilqr_steer_into appends its own rows."""
+        M, K, N, nal, L = geometry
+        n, D, u8, i32 = 2 * self.nq, self.D, torch.uint8, torch.int32
+        return [(knot_obs, (K, N, D), None, "knot_obs"), (end_obs, (N, D), None, "end_obs"), (actions, (K, N, 2), None, "actions"),
+                (target, (M, D), None, "target"), (cost, (M,), None, "cost"), (act_nom, (K, M, 2), None, "act_nom"),
+                (obs_nom, (K, M, D), None, "obs_nom"), (end_nom, (M, D), None, "end_nom"), (lx, (n, L), None, "lx"), (lu, (2, L), None, "lu"),
+                (p_final, (n, M), None, "p_final"), (cand_cost, (nal, M), None, "cand_cost"), (done, (K, N), u8, "done"),
+                (choice, (M,), i32, "choice"), (index, (L,), i32, "index")]
+
+    def ilqr_line_search_into(self, knot_obs, end_obs, actions, target, Q, R, *, cost, choice, done=None, Q_final=None, always=False,
+                              act_nom=None, obs_nom=None, end_nom=None, lx=None, lu=None, p_final=None, index=None, cand_cost=None):
+        """Allocation-free line search of iLQR on tensors in the kernel's layouts (include/os2r_search.h: os2rs_ilqr_line_search;
+        the arithmetic and its order are spelled out there).  With M trajectories (target [M, D]), N = nalpha M candidate lanes
+        (lane i M + m: trajectory m under step size i), K knots, L = K M and n = 2nq: knot_obs [K, N, D], end_obs [N, D],
+        actions [K, N, 2] and done [K, N] uint8 (or None) are what the candidates' recorded rollout returned; Q, R and Q_final
+        (None: Q) host values as in ilqr_backward.  The nominal, updated in place where a trajectory accepted a candidate and left
+        alone elsewhere: cost [M] (required; a candidate must lower it unless always=True), act_nom [K, M, 2], obs_nom [K, M, D],
+        end_nom [M, D], lx [n, L], lu [2, L], p_final [n, M] (the last three as ilqr_backward_into reads them), each or None.
+        Written on every call: choice [M] int32 (the accepted candidate or -1, required), index [L] int32 (what
+        copy_envs_from(cand_knots, index) takes on the K M-lane knots handle) and cand_cost [nalpha, M], each or None.  Shapes,
+        dtypes, device and contiguity are checked before the library is called (it takes addresses)."""
+        what = "ilqr_line_search"
+        q, r, qf = self._search_cost(what, Q, R, Q_final)
+        geometry = M, K, N, nal, L = self._search_geometry(what, target, knot_obs)
+        if cost is None or choice is None:
+            raise ValueError(f"{what}: cost and choice are required")
+        self._outs(what, self._search_rows(geometry, knot_obs, end_obs, actions, done, target, cost, act_nom, obs_nom, end_nom, lx, lu,
+                                           p_final, choice, index, cand_cost))
+        if end_obs is None or actions is None:
+            raise ValueError(f"{what}: end_obs and actions are required")
+        _call(search, "os2rs_ilqr_line_search", "os2rs_last_error", C.byref(self._layout()), K, M, nal, search.ACCEPT_ALWAYS if always else 0,
+              _ptr(knot_obs), _ptr(end_obs), _ptr(actions), _ptr(done), _ptr(target), q, r, qf, _ptr(cost), _ptr(act_nom), _ptr(obs_nom),
+              _ptr(end_nom), _ptr(lx), _ptr(lu), _ptr(p_final), _ptr(choice), _ptr(index), _ptr(cand_cost), self._stream())
+
+    def ilqr_line_search(self, knot_obs, end_obs, actions, target, Q, R, *, nominal=None, done=None, Q_final=None,
+                         want_cand_cost: bool = True):
+        """The line search of iLQR for M trajectories in one launch (include/os2r_search.h: os2rs_ilqr_line_search): the cost
+        sum_k 1/2 e_k'Q e_k + 1/2 a_k'R a_k + 1/2 e_K'Q_final e_K of every candidate, e the observation minus target on the raw
+        slots, one accepted step size per trajectory, and the nominal updated in place where a step was accepted.  knot_obs
+        [K, nalpha M, D], end_obs [nalpha M, D], actions [K, nalpha M, 2] and done [K, nalpha M] are what the candidates'
+        recorded rollout_schedule returned (knot observations, row K-1 of obs, applied actions, done), target [M, D].
+        nominal=None: a new nominal is allocated and every candidate with a finite cost and no episode end is acceptable (with
+        one candidate per trajectory, the first nominal's own rollout, this initialises it); a dict: the one an earlier call
+        returned, updated in place -- a candidate must lower its trajectory's cost.  The dict holds cost [M], actions [K, M, 2],
+        obs [K, M, D], end_obs [M, D], lx [n, K M], lu [2, K M], p_final [n, M] (the kernel's layouts) and lx_view [K M, n],
+        lu_view [K M, 2], p_final_view [M, n], permuted views ilqr_backward takes without a copy.
+        -> (choice [M] int32: the accepted candidate or -1, index [K M] int32 for knots.copy_envs_from(cand_knots, index),
+        cand_cost [nalpha, M] or None, nominal)."""
+        what = "ilqr_line_search"
+        M, K, N, nal, L = self._search_geometry(what, target, knot_obs, one_refusal=True)     # (here too: it sizes what is allocated)
+        n = 2 * self.nq
+        always = nominal is None
+        if always:
+            nominal = dict(cost=self._new(M), actions=self._new(K, M, 2), obs=self._new(K, M, self.D), end_obs=self._new(M, self.D),
+                           lx=self._new(n, L), lu=self._new(2, L), p_final=self._new(n, M))
+            for name in ("lx", "lu", "p_final"):
+                nominal[name + "_view"] = nominal[name].permute(1, 0)
+            for t in nominal.values():           # a trajectory none of whose candidates is acceptable keeps zeros, not garbage
+                t.zero_()
+        else:
+            _nominal_dict(what, nominal, "None or the dict an earlier call")
+        choice, index = self._new(M, dtype=torch.int32), self._new(L, dtype=torch.int32)
+        cand_cost = self._new(nal, M) if want_cand_cost else None
+        self.ilqr_line_search_into(knot_obs, end_obs, actions, target, Q, R, cost=nominal["cost"], choice=choice, done=done, Q_final=Q_final,
+                                   always=always, act_nom=nominal["actions"], obs_nom=nominal["obs"], end_nom=nominal["end_obs"],
+                                   lx=nominal["lx"], lu=nominal["lu"], p_final=nominal["p_final"], index=index, cand_cost=cand_cost)
+        return choice, index, cand_cost, nominal
+
+    def ilqr_steer_into(self, knot_obs, end_obs, actions, target, Q, R, dv, alphas, *, cost, mu, status, choice, iters=None, done=None,
+                        Q_final=None, rule=None, act_nom=None, obs_nom=None, end_nom=None, lx=None, lu=None, p_final=None, index=None,
+                        cand_cost=None, **rule_kw):
+        """Allocation-free steered line search of iLQR on tensors in the kernel's layouts (include/os2r_steer.h: os2rt_ilqr_steer;
+        the arithmetic and its order are spelled out there): ilqr_line_search_into, every argument of which but `always` is
+        taken as there, plus, per trajectory and in the same launch, an Armijo test on the predicted change, the update of mu, a
+        convergence test and a freeze.  dv [K, 2, M] as ilqr_backward_into wrote it, alphas the candidates' step sizes (host
+        values, one per candidate); mu [M] (the handle's dtype), status [M] int32 (0 active, 1 converged, 2 stalled) and iters [M]
+        int32 (or None) are read and written.  The rule is a dict and / or keywords over gym_os2r_amd.steer.RULE_DEFAULTS: armijo,
+        shrink, grow, mu_floor, mu_start, mu_max, tol.  Shapes, dtypes, device and contiguity are checked before the library is
+        called (it takes addresses)."""
+        what = "ilqr_steer"
+        q, r, qf = self._search_cost(what, Q, R, Q_final)
+        the_rule = steer.rule(rule, **rule_kw)
+        geometry = M, K, N, nal, L = self._search_geometry(what, target, knot_obs)
+        al = self._ilqr_scalars(0.0, alphas, True, what)[1]
+        if len(al) != nal:
+            raise ValueError(f"{what}: {len(al)} alphas for {nal} candidates per trajectory")
+        if any(t is None for t in (end_obs, actions, dv, cost, mu, status, choice)):
+            raise ValueError(f"{what}: end_obs, actions, dv, cost, mu, status and choice are required")
+        rows = self._search_rows(geometry, knot_obs, end_obs, actions, done, target, cost, act_nom, obs_nom, end_nom, lx, lu, p_final, choice,
+                                 index, cand_cost)
+        self._outs(what, rows + [(dv, (K, 2, M), None, "dv"), (mu, (M,), None, "mu"), (status, (M,), torch.int32, "status"),
+                                 (iters, (M,), torch.int32, "iters")])
+        _call(steer, "os2rt_ilqr_steer", "os2rt_last_error", C.byref(self._layout()), K, M, nal, _ptr(knot_obs), _ptr(end_obs), _ptr(actions),
+              _ptr(done), _ptr(target), q, r, qf, _ptr(dv), al, C.byref(the_rule), _ptr(cost), _ptr(act_nom), _ptr(obs_nom), _ptr(end_nom),
+              _ptr(lx), _ptr(lu), _ptr(p_final), _ptr(mu), _ptr(status), _ptr(iters), _ptr(choice), _ptr(index), _ptr(cand_cost),
+              self._stream())
+
+    def ilqr_steer(self, knot_obs, end_obs, actions, target, Q, R, dv, alphas, *, nominal, done=None, Q_final=None, rule=None,
+                   want_cand_cost: bool = True, **rule_kw):
+        """The line search of iLQR for M trajectories that also steers every trajectory's regularisation, in one launch
+        (include/os2r_steer.h: os2rt_ilqr_steer): ilqr_line_search on the nominal an earlier call returned, with, per trajectory,
+        an Armijo test of the actual against the predicted change alpha dv[..., 0].sum(0) + alpha^2 dv[..., 1].sum(0) (rule
+        member armijo; 0: none), mu halved after an accepted step and raised after an iteration without one (shrink, grow,
+        mu_floor, mu_start, mu_max), a trajectory frozen once a step lowered its cost by no more than tol |cost| (status 1) or
+        its mu would pass mu_max (status 2).  dv [K, M, 2] as ilqr_backward returned it (its permuted view of the kernel's layout
+        is taken without a copy), alphas the step sizes ilqr_backward made the candidates' table for.  `nominal` is the dict
+        ilqr_line_search returned; mu [M] (zeros), status [M] int32 (zeros: active) and iters [M] int32 (zeros) are added to it
+        where missing and updated in place like the rest -- nominal["mu"] is what ilqr_backward(mu_dev=...) reads.  No host
+        value is read: iterations can be launched back to back.
+        -> (choice [M] int32: the accepted candidate or -1, index [K M] int32 for knots.copy_envs_from(cand_knots, index),
+        cand_cost [nalpha, M] or None, nominal)."""
+        what = "ilqr_steer"
+        M, K, N, nal, L = self._search_geometry(what, target, knot_obs, one_refusal=True)     # (here too: it sizes what is allocated)
+        _nominal_dict(what, nominal, "the dict ilqr_line_search (or an earlier call)")
+        # (dv arrives as the [K, M, 2] view ilqr_backward returned, not in the layout ilqr_steer_into checks: its own refusal)
+        if not isinstance(dv, torch.Tensor) or tuple(dv.shape) != (K, M, 2) or dv.dtype != self.dtype or dv.device != self.device:
+            raise ValueError(f"{what}: dv must be a {self.dtype} tensor of shape ({K}, {M}, 2) on {self.device}, as ilqr_backward returns it")
+        dv_k = dv.permute(0, 2, 1).contiguous()             # no copy for what ilqr_backward returned
+        for name, dtype in (("mu", self.dtype), ("status", torch.int32), ("iters", torch.int32)):
+            if nominal.get(name) is None:
+                nominal[name] = torch.zeros(M, dtype=dtype, device=self.device)
+        choice, index = self._new(M, dtype=torch.int32), self._new(L, dtype=torch.int32)
+        cand_cost = self._new(nal, M) if want_cand_cost else None
+        self.ilqr_steer_into(knot_obs, end_obs, actions, target, Q, R, dv_k, alphas, cost=nominal["cost"], mu=nominal["mu"],
+                             status=nominal["status"], choice=choice, iters=nominal["iters"], done=done, Q_final=Q_final, rule=rule,
+                             act_nom=nominal["actions"], obs_nom=nominal["obs"], end_nom=nominal["end_obs"], lx=nominal["lx"],
+                             lu=nominal["lu"], p_final=nominal["p_final"], index=index, cand_cost=cand_cost, **rule_kw)
+        return choice, index, cand_cost, nominal
+
+    # -- MPPI update ------------------------------------------------------------------------
+    def _mppi_lanes(self, what, actions, S):
+        """actions [K, S M, 2] of an MPPI update with S samples per robot -> (K, N = S M, M), checked."""
+        if not isinstance(actions, torch.Tensor) or actions.dim() != 3:
+            raise ValueError(f"{what}: actions must be a tensor of shape (K, samples * M, 2)")
+        K, N = int(actions.shape[0]), int(actions.shape[1])
+        return K, N, _split(what, N, S, f"actions [{K} knots]", "samples", ok=K >= 1)
+
+    def mppi_update_into(self, returns, actions, nominal_in, nominal_out, *, samples: int, temperature: float, shift: int = 1,
+                         tail: str = "hold", applied=None, table=None, weights=None, ess=None, count=None):
+        """Allocation-free MPPI update on tensors in the kernel's layouts (include/os2r_mppi.h: os2rm_mppi_update; the arithmetic
+        and its order are spelled out there).  With S = samples, M robots, N = S M lanes (lane s M + m: sample s of robot m) and K
+        knots: returns [N], actions [K, N, 2] and nominal_in [K, M, 2] are read; nominal_out [K, M, 2] (required, another tensor
+        than nominal_in), applied [M, 2], table [K, 2, D+1, N] (only its bias entries [:, :, D, :] are written), weights [S, M],
+        ess [M] and count [M] int32 are written, each of the last five or None.  temperature > 0 is the softmax temperature of
+        the returns (beta = 1 / temperature), shift in 0..K, tail "hold" or "zero".  Shapes, dtypes, device and contiguity are
+        checked before the library is called (it takes addresses)."""
+        what = "mppi_update"
+        S = _count(what, "samples", samples)
+        temp = _finite(what, "temperature", temperature, _invertible, "> 0")
+        if tail not in mppi.TAILS:
+            raise ValueError(f"{what}: tail must be 'hold' or 'zero', got {tail!r}")
+        K, N, M = self._mppi_lanes(what, actions, S)
+        if isinstance(shift, bool) or not isinstance(shift, int) or not 0 <= shift <= K:
+            raise ValueError(f"{what}: shift must be an integer in 0..{K}, got {shift!r}")
+        if returns is None or nominal_in is None or nominal_out is None:
+            raise ValueError(f"{what}: returns, nominal_in and nominal_out are required")
+        self._outs(what, ((returns, (N,), None, "returns"), (actions, (K, N, 2), None, "actions"), (nominal_in, (K, M, 2), None, "nominal_in"),
+                          (nominal_out, (K, M, 2), None, "nominal_out"), (applied, (M, 2), None, "applied"),
+                          (table, (K, 2, self.D + 1, N), None, "table"), (weights, (S, M), None, "weights"), (ess, (M,), None, "ess"),
+                          (count, (M,), torch.int32, "count")))
+        if nominal_out.data_ptr() == nominal_in.data_ptr():
+            raise ValueError(f"{what}: nominal_out must be another tensor than nominal_in (every slot reads its source slot itself)")
+        _call(mppi, "os2rm_mppi_update", "os2rm_last_error", C.byref(self._layout()), K, M, S, _ptr(returns), _ptr(actions), _ptr(nominal_in),
+              1.0 / temp, shift, mppi.TAILS[tail], _ptr(nominal_out), _ptr(applied), _ptr(table), _ptr(weights), _ptr(ess), _ptr(count),
+              self._stream())
+
+    def mppi_update(self, returns, actions, nominal, *, samples: int, temperature: float, shift: int = 1, tail: str = "hold",
+                    table=None, want_weights: bool = False, want_ess: bool = False):
+        """The MPPI update of M robots in one launch (include/os2r_mppi.h: os2rm_mppi_update): with S = samples and N = S M lanes,
+        lane s M + m sample s of robot m -- a planner handle forked by copy_envs_from(real, arange(N) % M) --, returns [N] and
+        actions [K, N, 2] are what the noisy rollout_schedule(first_episode=True, want_actions=True) returned and nominal
+        [K, M, 2] the nominal its table held.  Every robot's lanes with a finite return are weighted by
+        exp((return - max) / temperature); the new nominal is the weighted mean of their action sequences clipped to [-1, 1] (a
+        robot without a valid lane keeps its nominal), moved `shift` slots towards the present with the last slot held
+        (tail="hold") or zeros behind it (tail="zero").
+        table: None (no table), True (this handle's own [N, K, 2, D+1] table, allocated as zeros at the first call and kept) or
+        the table an earlier call or ilqr_backward(want_weights=True) returned -- a permuted view of the kernel's
+        [K, 2, D+1, N] layout; only its bias entries table[:, :, :, D] are written, to the new nominal of the lane's robot: the
+        weights of the next rollout_schedule, which then applies clip(nominal + sigma eps).
+        The new nominal is written into one of two buffers the handle keeps for this shape, the one `nominal` is not: feed it
+        back and the two alternate.
+        -> (applied [M, 2]: slot 0 of the weighted mean, the action for real.step; nominal [K, M, 2]; table [N, K, 2, D+1] | None;
+        weights [S, M] | None: the unnormalised weights; ess [M] | None: the effective sample size; count [M] int32: the valid
+        lanes of every robot)."""
+        what = "mppi_update"
+        S, R = _count(what, "samples", samples), self.D + 1
+        K, N, M = self._mppi_lanes(what, actions, S)                      # (here too, both: they size what is allocated)
+        self._out(nominal, (K, M, 2), self.dtype, f"{what}: nominal")
+        if nominal is None:
+            raise ValueError(f"{what}: nominal is required")
+        tab = None
+        if table is True:
+            tables = self.__dict__.setdefault("_mppi_tables", {})
+            if (K, N) not in tables:
+                tables[(K, N)] = torch.zeros(K, 2, R, N, dtype=self.dtype, device=self.device)
+            tab = tables[(K, N)]
+        elif table is not None and table is not False:
+            if (not isinstance(table, torch.Tensor) or tuple(table.shape) != (N, K, 2, R) or table.dtype != self.dtype
+                    or table.device != self.device or not table.permute(1, 2, 3, 0).is_contiguous()):
+                raise ValueError(f"{what}: table must be None, True or a {self.dtype} tensor of shape ({N}, {K}, 2, {R}) on {self.device} "
+                                 f"that is a permuted view of the kernel's [K, 2, D+1, N] layout, as an earlier call returned it")
+            tab = table.permute(1, 2, 3, 0)
+        out = self._other_buffer("_mppi_nominals", (K, M, 2), nominal)
+        applied, count = self._new(M, 2), self._new(M, dtype=torch.int32)
+        weights = self._new(S, M) if want_weights else None
+        ess = self._new(M) if want_ess else None
+        self.mppi_update_into(returns, actions, nominal, out, samples=S, temperature=temperature, shift=shift, tail=tail,
+                              applied=applied, table=tab, weights=weights, ess=ess, count=count)
+        return applied, out, (None if tab is None else tab.permute(3, 0, 1, 2)), weights, ess, count
+
+    # -- particle-filter update -------------------------------------------------------------
+    def _pf_lanes(self, what, obs, S):
+        """obs [S M, D] of a particle-filter update with S particles per robot -> (N = S M, M), checked."""
+        if not isinstance(obs, torch.Tensor) or obs.dim() != 2:
+            raise ValueError(f"{what}: obs must be a tensor of shape (particles * M, {self.D})")
+        N = int(obs.shape[0])
+        return N, _split(what, N, S, "obs", "particles")
+
+    def pf_update_into(self, obs, meas, prec, logw_out, index, *, particles: int, logw_in=None, u=None, resample_ratio: float = 0.5,
+                       est=None, weights=None, ess=None, count=None, resampled=None):
+        """Allocation-free particle-filter update on tensors in the kernel's layouts (include/os2r_pf.h: os2rp_pf_update; the
+        arithmetic and its order are spelled out there).  With S = particles, M robots and N = S M lanes (lane s M + m: particle s
+        of robot m): obs [N, D], meas [M, D], prec [D], logw_in [S, M] (None: zeros) and u [M] (None: 0.5) are read; logw_out
+        [S, M] (required, another tensor than logw_in), index [N] int32 (required), est [M, D], weights [S, M], ess [M], count [M]
+        int32 and resampled [M] int32 are written, each of the last five or None.  resample_ratio is finite and >= 0.  Shapes,
+        dtypes, device and contiguity are checked before the library is called (it takes addresses)."""
+        what = "pf_update"
+        S, D, i32 = _count(what, "particles", particles), self.D, torch.int32
+        # (a bool is no ratio: refused in the words of a value that is not finite)
+        ratio = _finite(what, "resample_ratio", math.nan if isinstance(resample_ratio, bool) else resample_ratio, _not_negative, ">= 0",
+                        repr(resample_ratio))
+        N, M = self._pf_lanes(what, obs, S)
+        if meas is None or prec is None or logw_out is None or index is None:
+            raise ValueError(f"{what}: obs, meas, prec, logw_out and index are required")
+        self._outs(what, ((obs, (N, D), None, "obs"), (meas, (M, D), None, "meas"), (prec, (D,), None, "prec"), (logw_in, (S, M), None, "logw_in"),
+                          (u, (M,), None, "u"), (logw_out, (S, M), None, "logw_out"), (est, (M, D), None, "est"),
+                          (weights, (S, M), None, "weights"), (ess, (M,), None, "ess"), (index, (N,), i32, "index"), (count, (M,), i32, "count"),
+                          (resampled, (M,), i32, "resampled")))
+        if logw_in is not None and logw_out.data_ptr() == logw_in.data_ptr():
+            raise ValueError(f"{what}: logw_out must be another tensor than logw_in (the launch keeps the weights in it between its passes)")
+        _call(pf, "os2rp_pf_update", "os2rp_last_error", C.byref(self._layout()), M, S, _ptr(obs), _ptr(meas), _ptr(prec), _ptr(logw_in), _ptr(u),
+              ratio, _ptr(logw_out), _ptr(index), _ptr(est), _ptr(weights), _ptr(ess), _ptr(count), _ptr(resampled), self._stream())
+
+    def pf_update(self, obs, meas, prec, *, particles: int, logw=None, u=None, resample_ratio: float = 0.5, want_estimate: bool = True,
+                  want_weights: bool = False):
+        """The particle-filter update of M robots in one launch (include/os2r_pf.h: os2rp_pf_update): with S = particles and
+        N = S M lanes, lane s M + m particle s of robot m -- a particle handle forked by copy_envs_from(real, arange(N) % M) --,
+        obs [N, D] is every particle's observation as step, a one-step rollout or copy_envs_from returned it, meas [M, D] the
+        measurement of every robot and prec [D] one inverse variance per observation entry (0 drops the entry).  Every particle's
+        log-weight is logw [S, M] (None: zeros) minus half its precision-weighted squared distance from the measurement; a
+        particle whose log-weight is not finite is invalid and has weight 0.  A robot resamples when its effective sample size
+        falls below resample_ratio * S or when it holds an invalid particle: systematic resampling with the offset u [M] in
+        [0, 1) (None: 0.5), after which its log-weights are 0.  A robot without a valid particle is lost: nothing moves, its
+        log-weights are 0 and its estimate is the measurement.
+        The new log-weights are written into one of two buffers the handle keeps for this shape, the one `logw` is not: feed
+        them back and the two alternate.
+        -> (logw [S, M]: normalised to a maximum of 0, -inf for an invalid particle; index [N] int32 for
+        self.copy_envs_from(self, index): the ancestor of every lane, -1 (keep) in the lanes of a robot that did not resample;
+        est [M, D] | None: the weighted mean observation; weights [S, M] | None: the unnormalised weights; ess [M]: the effective
+        sample size; count [M] int32: the valid particles of every robot; resampled [M] int32: 1 where the robot resampled)."""
+        what = "pf_update"
+        S = _count(what, "particles", particles)
+        N, M = self._pf_lanes(what, obs, S)                               # (here too, both: they size what is allocated)
+        self._out(logw, (S, M), self.dtype, f"{what}: logw")              # (and logw here: its address picks the buffer)
+        out = self._other_buffer("_pf_logw", (S, M), logw)
+        index = self._new(N, dtype=torch.int32)
+        est = self._new(M, self.D) if want_estimate else None
+        weights = self._new(S, M) if want_weights else None
+        ess, count, resampled = self._new(M), self._new(M, dtype=torch.int32), self._new(M, dtype=torch.int32)
+        self.pf_update_into(obs, meas, prec, out, index, particles=S, logw_in=logw, u=u, resample_ratio=resample_ratio, est=est,
+                            weights=weights, ess=ess, count=count, resampled=resampled)
+        return out, index, est, weights, ess, count, resampled

@@ -9,14 +9,9 @@ the library has not been built (``make -C gym-os2r_amd/csrc``), load() raises.
 from __future__ import annotations
 
 import ctypes as C
-import os
 
-from ._lib import load_library
+from ._lib import companion as _companion
 from .control import MAX_OBS, Os2rControlLayout, layout  # noqa: F401  (re-exported)
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("OS2R_PF_LIBRARY") or os.path.join(_HERE, "libos2r_pf.so")
-_lib = None
 
 ABI_VERSION = 1          # OS2R_PF_ABI_VERSION
 CHUNKS = 8               # OS2RP_CHUNKS
@@ -38,10 +33,5 @@ class Os2rPfLibraryMissing(ImportError):
     pass
 
 
-def load():
-    global _lib
-    if _lib is None:
-        _lib = load_library(LIB_PATH, ENTRY_POINTS, "os2rp_last_error", ("os2rp_abi_version", ABI_VERSION), Os2rPfLibraryMissing,
-                            "build the HIP extension first (make -C gym-os2r_amd/csrc). There is no CPU fallback.",
-                            "libos2r_pf.so ABI version does not match gym_os2r_amd.pf")
-    return _lib
+# the library through ctypes, loaded once; OS2R_PF_LIBRARY: A/B builds of the same ABI
+LIB_PATH, load = _companion(globals(), "os2r_pf", "os2rp", "OS2R_PF_LIBRARY", Os2rPfLibraryMissing)

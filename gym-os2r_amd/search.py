@@ -9,14 +9,9 @@ no fallback: if the library has not been built (``make -C gym-os2r_amd/csrc``), 
 from __future__ import annotations
 
 import ctypes as C
-import os
 
-from ._lib import load_library
+from ._lib import companion as _companion
 from .control import MAX_ALPHAS, MAX_OBS, Os2rControlLayout, layout, slot_columns  # noqa: F401  (re-exported)
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("OS2R_SEARCH_LIBRARY") or os.path.join(_HERE, "libos2r_search.so")
-_lib = None
 
 ABI_VERSION = 1          # OS2R_SEARCH_ABI_VERSION
 ACCEPT_ALWAYS = 1        # OS2RS_ACCEPT_ALWAYS
@@ -38,10 +33,5 @@ class Os2rSearchLibraryMissing(ImportError):
     pass
 
 
-def load():
-    global _lib
-    if _lib is None:
-        _lib = load_library(LIB_PATH, ENTRY_POINTS, "os2rs_last_error", ("os2rs_abi_version", ABI_VERSION), Os2rSearchLibraryMissing,
-                            "build the HIP extension first (make -C gym-os2r_amd/csrc). There is no CPU fallback.",
-                            "libos2r_search.so ABI version does not match gym_os2r_amd.search")
-    return _lib
+# the library through ctypes, loaded once; OS2R_SEARCH_LIBRARY: A/B builds of the same ABI
+LIB_PATH, load = _companion(globals(), "os2r_search", "os2rs", "OS2R_SEARCH_LIBRARY", Os2rSearchLibraryMissing)

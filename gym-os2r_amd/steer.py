@@ -10,14 +10,9 @@ fallback: if the library has not been built (``make -C gym-os2r_amd/csrc``), loa
 from __future__ import annotations
 
 import ctypes as C
-import os
 
-from ._lib import load_library
+from ._lib import companion as _companion
 from .control import MAX_ALPHAS, MAX_OBS, Os2rControlLayout, layout, slot_columns  # noqa: F401  (re-exported)
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("OS2R_STEER_LIBRARY") or os.path.join(_HERE, "libos2r_steer.so")
-_lib = None
 
 ABI_VERSION = 1          # OS2R_STEER_ABI_VERSION
 ACTIVE, CONVERGED, STALLED = 0, 1, 2   # OS2RT_ACTIVE, OS2RT_CONVERGED, OS2RT_STALLED
@@ -52,13 +47,8 @@ class Os2rSteerLibraryMissing(ImportError):
     pass
 
 
-def load():
-    global _lib
-    if _lib is None:
-        _lib = load_library(LIB_PATH, ENTRY_POINTS, "os2rt_last_error", ("os2rt_abi_version", ABI_VERSION), Os2rSteerLibraryMissing,
-                            "build the HIP extension first (make -C gym-os2r_amd/csrc). There is no CPU fallback.",
-                            "libos2r_steer.so ABI version does not match gym_os2r_amd.steer")
-    return _lib
+# the library through ctypes, loaded once; OS2R_STEER_LIBRARY: A/B builds of the same ABI
+LIB_PATH, load = _companion(globals(), "os2r_steer", "os2rt", "OS2R_STEER_LIBRARY", Os2rSteerLibraryMissing)
 
 
 def rule(rule=None, **kw):
