@@ -1,5 +1,5 @@
 """The controller calls of a HipSim: LQR gains, the iLQR backward pass, its line search with and without a steered mu, the MPPI
-update, the particle-filter update and the Kalman filter update, each as an allocation-free ``*_into`` on tensors in the kernel's layout and an allocating
+update, the particle-filter update, the Kalman filter update and the two calls of the unscented Kalman filter (its sigma points and its update), each as an allocation-free ``*_into`` on tensors in the kernel's layout and an allocating
 wrapper around it.  ``Controllers`` is the plain base class HipSim (gym_os2r_amd.sim) inherits them from; it uses the handle's
 ``_out``, ``_in``, ``_new``, ``_layout``, ``_stream`` and ``_check``.
 
@@ -14,7 +14,7 @@ import math
 
 import torch
 
-from . import abi, control, ekf, mppi, pf, search, steer
+from . import abi, control, ekf, mppi, pf, search, steer, ukf
 from ._lib import Os2rError, _ptr
 
 NOMINAL_KEYS = ("cost", "actions", "obs", "end_obs", "lx", "lu", "p_final")
@@ -706,3 +706,148 @@ class Controllers:
         innov = self._new(M, D) if want_innov else None
         self.ekf_update_into(x_pred, p_in, meas, prec, x_out, p_out, A=a, Q=Q, gate=gate, nis=nis, used=used, refused=refused, innov=innov)
         return x_out, p_out.permute(2, 0, 1), nis, used, refused, innov
+
+    # -- unscented Kalman filter: sigma points and update ---------------------------------------
+    def _ukf_weights(self, what, alpha, beta, kappa):
+        """gym_os2r_amd.ukf.weights for this handle's 2nq states -> (gamma, wm0, wc0, wi), its refusals naming the method `what`."""
+        try:
+            return ukf.weights(2 * self.nq, alpha, beta, kappa)
+        except ValueError as e:
+            raise ValueError(f"{what}: {e}") from None
+
+    def _kernel_view(self, what, t, shape, name, perm):
+        """`t` of `shape` as the kernel takes it, `perm` applied: a permuted view of the kernel's layout goes on without a copy,
+        anything else is converted and copied once; None stays None."""
+        if t is None:
+            return None
+        if (isinstance(t, torch.Tensor) and t.dtype == self.dtype and t.device == self.device and tuple(t.shape) == tuple(shape)
+                and t.permute(*perm).is_contiguous()):
+            return t.permute(*perm)
+        try:
+            return self._in(t, shape).permute(*perm).contiguous()
+        except (ValueError, TypeError, RuntimeError) as e:
+            raise ValueError(f"{what}: {name}: {e}") from None
+
+    def ukf_points_into(self, x, P, points_out, *, failed=None, alpha: float = 1.0, beta: float = 2.0, kappa: float = 0.0):
+        """Allocation-free sigma points on tensors in the kernel's layouts (include/os2r_ukf.h: os2ru_ukf_points; the arithmetic
+        and its order are spelled out there), the robot index fastest.  With M = x.shape[1] robots (it need not be the handle's
+        N), n = 2nq and S = 2n + 1: x [n, M] and P [n, n, M] (its upper triangle) are read; points_out [n, S M] (required; lane
+        s M + m is point s of robot m) and failed [M] int32 (or None: 0, or j + 1 where the Cholesky factor failed at column j --
+        all points of that robot are x) are written.  alpha, beta, kappa: gym_os2r_amd.ukf.weights.  Shapes, dtypes, device and
+        contiguity are checked before the library is called (it takes addresses)."""
+        what = "ukf_points"
+        n = 2 * self.nq
+        S = ukf.npoints(self.nq)
+        gamma = self._ukf_weights(what, alpha, beta, kappa)[0]
+        if not isinstance(x, torch.Tensor) or x.dim() != 2 or int(x.shape[1]) < 1:
+            raise ValueError(f"{what}: x must be a tensor of shape ({n}, M)")
+        M = int(x.shape[1])
+        if P is None or points_out is None:
+            raise ValueError(f"{what}: x, P and points_out are required")
+        self._outs(what, ((x, (n, M), None, "x"), (P, (n, n, M), None, "P"), (points_out, (n, S * M), None, "points_out"),
+                          (failed, (M,), torch.int32, "failed")))
+        _call(ukf, "os2ru_ukf_points", "os2ru_last_error", C.byref(self._layout()), M, _ptr(x), _ptr(P), gamma, _ptr(points_out), _ptr(failed),
+              self._stream())
+
+    def ukf_points(self, x, P, *, alpha: float = 1.0, beta: float = 2.0, kappa: float = 0.0, want_failed: bool = True):
+        """The 2n + 1 sigma points of M robots in one launch (include/os2r_ukf.h: os2ru_ukf_points): a Cholesky factor L of every
+        robot's P, then x, x + gamma L[:, j] and x - gamma L[:, j].  x [2nq, M]; P [M, 2nq, 2nq] -- what ukf_update returned
+        is a permuted view of the kernel's layout and goes on without a copy, anything else is converted and copied once; only
+        its upper triangle is read.  alpha, beta, kappa: gym_os2r_amd.ukf.weights (the defaults give gamma = sqrt(2nq)).
+        -> (points [2nq, S M] with S = 4nq + 1, lane s M + m point s of robot m: points[:nq] and points[nq:] are what
+        set_state takes on a sigma handle of S M lanes forked by copy_envs_from(real, arange(S M) % M); failed [M] int32 | None:
+        0, or j + 1 where the factor met a pivot that is not positive and finite at column j -- that robot's points all equal x)."""
+        what = "ukf_points"
+        n = 2 * self.nq
+        self._ukf_weights(what, alpha, beta, kappa)                           # (here too: before anything is copied or allocated)
+        if not isinstance(x, torch.Tensor) or x.dim() != 2 or int(x.shape[1]) < 1:
+            raise ValueError(f"{what}: x must be a tensor of shape ({n}, M)")
+        M = int(x.shape[1])
+        if P is None:
+            raise ValueError(f"{what}: P is required")
+        p = self._kernel_view(what, P, (M, n, n), "P", (1, 2, 0))
+        points = self._new(n, ukf.npoints(self.nq) * M)
+        failed = self._new(M, dtype=torch.int32) if want_failed else None
+        self.ukf_points_into(x, p, points, failed=failed, alpha=alpha, beta=beta, kappa=kappa)
+        return points, failed
+
+    def _ukf_state(self, what, state, meas):
+        """state, the pair (q, qd) of get_state() on the sigma handle, and meas [M, D] of an unscented update -> (q, qd, M, lanes)."""
+        S = ukf.npoints(self.nq)
+        if not (isinstance(state, (tuple, list)) and len(state) == 2 and all(isinstance(t, torch.Tensor) and t.dim() == 2 for t in state)):
+            raise ValueError(f"{what}: state must be the pair (q, qd) of get_state(), two tensors of shape ({self.nq}, {S} * M)")
+        if not isinstance(meas, torch.Tensor) or meas.dim() != 2 or int(meas.shape[0]) < 1:
+            raise ValueError(f"{what}: meas must be a tensor of shape (M, {self.D})")
+        M, lanes = int(meas.shape[0]), int(state[0].shape[1])
+        _split(what, lanes, S, f"state [{M} robots in meas]", "points", ok=lanes == S * M)
+        return state[0], state[1], M, lanes
+
+    def ukf_update_into(self, state, P_in, meas, prec, x_out, P_out, *, Q, done=None, gate: float = 0.0, alpha: float = 1.0,
+                        beta: float = 2.0, kappa: float = 0.0, nis=None, used=None, refused=None, innov=None, lost=None, points_out=None,
+                        failed=None):
+        """Allocation-free unscented Kalman filter update on tensors in the kernel's layouts (include/os2r_ukf.h:
+        os2ru_ukf_update; the arithmetic and its order are spelled out there), the robot index fastest.  With M = meas.shape[0]
+        robots (it need not be the handle's N), n = 2nq and S = 2n + 1: state, the pair (q, qd) as get_state() returned it on the
+        sigma handle after its step ([nq, S M] each, taken as they are), done [S M] uint8 (that step's flags, or None),
+        P_in [n, n, M] (its upper triangle; used for lost robots only), meas [M, D] and prec [D] are read; x_out [n, M] (required),
+        P_out [n, n, M] (required; may be P_in), nis [M], used [M] int32, refused [M] int32, innov [M, D], lost [M] int32,
+        points_out [n, S M] (the sigma points of the result) and failed [M] int32 (only with points_out) are written, each of the
+        last seven or None.  Q [n, n] (host values, finite, exactly symmetric) is the additive process noise, gate finite and
+        >= 0 (0: none), alpha, beta, kappa: gym_os2r_amd.ukf.weights.  Shapes, dtypes, device and contiguity are checked before the
+        library is called (it takes addresses)."""
+        what = "ukf_update"
+        n, D, i32 = 2 * self.nq, self.D, torch.int32
+        nq, S = self.nq, ukf.npoints(self.nq)
+        if Q is None:
+            raise ValueError(f"{what}: Q is required (the additive process noise)")
+        q_host, gate = self._ekf_scalars(what, True, Q, gate)
+        gamma, wm0, wc0, wi = self._ukf_weights(what, alpha, beta, kappa)
+        q, qd, M, lanes = self._ukf_state(what, state, meas)
+        if P_in is None or prec is None or x_out is None or P_out is None:
+            raise ValueError(f"{what}: state, P_in, meas, prec, x_out and P_out are required")
+        if failed is not None and points_out is None:
+            raise ValueError(f"{what}: failed needs points_out (it is the verdict on their Cholesky factor)")
+        self._outs(what, ((q, (nq, lanes), None, "state[0]"), (qd, (nq, lanes), None, "state[1]"), (done, (lanes,), torch.uint8, "done"),
+                          (P_in, (n, n, M), None, "P_in"), (meas, (M, D), None, "meas"), (prec, (D,), None, "prec"),
+                          (x_out, (n, M), None, "x_out"), (P_out, (n, n, M), None, "P_out"), (nis, (M,), None, "nis"),
+                          (innov, (M, D), None, "innov"), (used, (M,), i32, "used"), (refused, (M,), i32, "refused"), (lost, (M,), i32, "lost"),
+                          (points_out, (n, lanes), None, "points_out"), (failed, (M,), i32, "failed")))
+        _call(ukf, "os2ru_ukf_update", "os2ru_last_error", C.byref(self._layout()), M, _ptr(q), _ptr(qd), _ptr(done), _ptr(P_in), q_host, gamma,
+              wm0, wc0, wi, _ptr(meas), _ptr(prec), gate, _ptr(x_out), _ptr(P_out), _ptr(nis), _ptr(used), _ptr(refused), _ptr(innov),
+              _ptr(lost), _ptr(points_out), _ptr(failed), self._stream())
+
+    def ukf_update(self, state, P, meas, prec, *, Q, done=None, gate: float = 0.0, alpha: float = 1.0, beta: float = 2.0, kappa: float = 0.0,
+                   want_innov: bool = False, want_points: bool = True):
+        """The unscented Kalman filter update of M robots in one launch (include/os2r_ukf.h: os2ru_ukf_update).  On a sigma
+        handle of S M lanes (S = 4nq + 1, forked by copy_envs_from(real, arange(S M) % M)),
+        sig.set_state(points[:nq], points[nq:]) -> sig.step(action tiled S times) -> sig.get_state() -> ukf_update is one filter
+        step for every robot, and needs no Jacobian.  state: the pair (q, qd) get_state() returned, taken without a copy; done: the
+        step's done flags [S M] uint8 (None: none).  The mean and covariance of every robot's propagated points are formed with the
+        weights of gym_os2r_amd.ukf.weights(2nq, alpha, beta, kappa) and Q [2nq, 2nq] (host values, finite, exactly symmetric) is
+        added; then the measurement update of ekf_update against meas [M, D] with prec [D] and gate.  A robot one of whose lanes
+        is done or not finite is lost: its x is point 0 and its covariance the P it came with.  P [M, 2nq, 2nq] as an earlier call
+        returned it is a permuted view of the kernel's layout and goes on without a copy, anything else is converted and copied
+        once.  The new covariance is written into one of two buffers the handle keeps for this shape, the one `P` is not in: feed
+        it back and the two alternate.
+        -> (x [2nq, M]; P [M, 2nq, 2nq]; nis [M]; used [M] int32; refused [M] int32; innov [M, D] | None; lost [M] int32: 1 where
+        the robot was lost; points [2nq, S M] | None: the sigma points of the new (x, P), what the next set_state takes;
+        failed [M] int32 | None: as ukf_points returns it, with the points)."""
+        what = "ukf_update"
+        n, D, S = 2 * self.nq, self.D, ukf.npoints(self.nq)
+        if Q is None:
+            raise ValueError(f"{what}: Q is required (the additive process noise)")
+        self._ekf_scalars(what, True, Q, gate)                                # (here too: before anything is copied or allocated)
+        self._ukf_weights(what, alpha, beta, kappa)
+        q, qd, M, lanes = self._ukf_state(what, state, meas)                  # (and M: it sizes what is allocated)
+        if P is None:
+            raise ValueError(f"{what}: P is required")
+        p_in = self._kernel_view(what, P, (M, n, n), "P", (1, 2, 0))
+        p_out = self._other_buffer("_ukf_covariances", (n, n, M), p_in)
+        x_out, nis = self._new(n, M), self._new(M)
+        used, refused, lost = (self._new(M, dtype=torch.int32) for _ in range(3))
+        innov = self._new(M, D) if want_innov else None
+        points = self._new(n, lanes) if want_points else None
+        failed = self._new(M, dtype=torch.int32) if want_points else None
+        self.ukf_update_into((q, qd), p_in, meas, prec, x_out, p_out, Q=Q, done=done, gate=gate, alpha=alpha, beta=beta, kappa=kappa, nis=nis,
+                             used=used, refused=refused, innov=innov, lost=lost, points_out=points, failed=failed)
+        return x_out, p_out.permute(2, 0, 1), nis, used, refused, innov, lost, points, failed
