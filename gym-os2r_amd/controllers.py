@@ -1,5 +1,5 @@
 """The controller calls of a HipSim: LQR gains, the iLQR backward pass, its line search with and without a steered mu, the MPPI
-update, the particle-filter update, the Kalman filter update and the two calls of the unscented Kalman filter (its sigma points and its update), each as an allocation-free ``*_into`` on tensors in the kernel's layout and an allocating
+update, the cross-entropy update, the particle-filter update, the Kalman filter update and the two calls of the unscented Kalman filter (its sigma points and its update), each as an allocation-free ``*_into`` on tensors in the kernel's layout and an allocating
 wrapper around it.  ``Controllers`` is the plain base class HipSim (gym_os2r_amd.sim) inherits them from; it uses the handle's
 ``_out``, ``_in``, ``_new``, ``_layout``, ``_stream`` and ``_check``.
 
@@ -14,7 +14,7 @@ import math
 
 import torch
 
-from . import abi, control, ekf, mppi, pf, search, steer, ukf
+from . import abi, cem, control, ekf, mppi, pf, search, steer, ukf
 from ._lib import Os2rError, _ptr
 
 NOMINAL_KEYS = ("cost", "actions", "obs", "end_obs", "lx", "lu", "p_final")
@@ -59,6 +59,13 @@ def _not_negative(x):
 
 def _invertible(x):
     return x > 0.0 and math.isfinite(1.0 / x)
+
+
+def _shift(what, shift, K):
+    """`shift` of a sampling planner's update with K knots: an integer in 0..K and no bool."""
+    if isinstance(shift, bool) or not isinstance(shift, int) or not 0 <= shift <= K:
+        raise ValueError(f"{what}: shift must be an integer in 0..{K}, got {shift!r}")
+    return shift
 
 
 def _nominal_dict(what, nominal, wanted):
@@ -484,6 +491,24 @@ class Controllers:
         K, N = int(actions.shape[0]), int(actions.shape[1])
         return K, N, _split(what, N, S, f"actions [{K} knots]", "samples", ok=K >= 1)
 
+    def _planner_table(self, what, kept, table, K, N):
+        """`table` of a sampling planner's update -> the table in the kernel's [K, 2, D+1, N] layout, or None: None or False (no
+        table), True (this handle's own, allocated as zeros at the first call and kept in its dict `kept`) or the [N, K, 2, D+1]
+        view an earlier call returned."""
+        R = self.D + 1
+        if table is True:
+            tables = self.__dict__.setdefault(kept, {})
+            if (K, N) not in tables:
+                tables[(K, N)] = torch.zeros(K, 2, R, N, dtype=self.dtype, device=self.device)
+            return tables[(K, N)]
+        if table is None or table is False:
+            return None
+        if (not isinstance(table, torch.Tensor) or tuple(table.shape) != (N, K, 2, R) or table.dtype != self.dtype
+                or table.device != self.device or not table.permute(1, 2, 3, 0).is_contiguous()):
+            raise ValueError(f"{what}: table must be None, True or a {self.dtype} tensor of shape ({N}, {K}, 2, {R}) on {self.device} "
+                             f"that is a permuted view of the kernel's [K, 2, D+1, N] layout, as an earlier call returned it")
+        return table.permute(1, 2, 3, 0)
+
     def mppi_update_into(self, returns, actions, nominal_in, nominal_out, *, samples: int, temperature: float, shift: int = 1,
                          tail: str = "hold", applied=None, table=None, weights=None, ess=None, count=None):
         """Allocation-free MPPI update on tensors in the kernel's layouts (include/os2r_mppi.h: os2rm_mppi_update; the arithmetic
@@ -499,8 +524,7 @@ class Controllers:
         if tail not in mppi.TAILS:
             raise ValueError(f"{what}: tail must be 'hold' or 'zero', got {tail!r}")
         K, N, M = self._mppi_lanes(what, actions, S)
-        if isinstance(shift, bool) or not isinstance(shift, int) or not 0 <= shift <= K:
-            raise ValueError(f"{what}: shift must be an integer in 0..{K}, got {shift!r}")
+        _shift(what, shift, K)
         if returns is None or nominal_in is None or nominal_out is None:
             raise ValueError(f"{what}: returns, nominal_in and nominal_out are required")
         self._outs(what, ((returns, (N,), None, "returns"), (actions, (K, N, 2), None, "actions"), (nominal_in, (K, M, 2), None, "nominal_in"),
@@ -532,23 +556,12 @@ class Controllers:
         weights [S, M] | None: the unnormalised weights; ess [M] | None: the effective sample size; count [M] int32: the valid
         lanes of every robot)."""
         what = "mppi_update"
-        S, R = _count(what, "samples", samples), self.D + 1
+        S = _count(what, "samples", samples)
         K, N, M = self._mppi_lanes(what, actions, S)                      # (here too, both: they size what is allocated)
         self._out(nominal, (K, M, 2), self.dtype, f"{what}: nominal")
         if nominal is None:
             raise ValueError(f"{what}: nominal is required")
-        tab = None
-        if table is True:
-            tables = self.__dict__.setdefault("_mppi_tables", {})
-            if (K, N) not in tables:
-                tables[(K, N)] = torch.zeros(K, 2, R, N, dtype=self.dtype, device=self.device)
-            tab = tables[(K, N)]
-        elif table is not None and table is not False:
-            if (not isinstance(table, torch.Tensor) or tuple(table.shape) != (N, K, 2, R) or table.dtype != self.dtype
-                    or table.device != self.device or not table.permute(1, 2, 3, 0).is_contiguous()):
-                raise ValueError(f"{what}: table must be None, True or a {self.dtype} tensor of shape ({N}, {K}, 2, {R}) on {self.device} "
-                                 f"that is a permuted view of the kernel's [K, 2, D+1, N] layout, as an earlier call returned it")
-            tab = table.permute(1, 2, 3, 0)
+        tab = self._planner_table(what, "_mppi_tables", table, K, N)
         out = self._other_buffer("_mppi_nominals", (K, M, 2), nominal)
         applied, count = self._new(M, 2), self._new(M, dtype=torch.int32)
         weights = self._new(S, M) if want_weights else None
@@ -556,6 +569,91 @@ class Controllers:
         self.mppi_update_into(returns, actions, nominal, out, samples=S, temperature=temperature, shift=shift, tail=tail,
                               applied=applied, table=tab, weights=weights, ess=ess, count=count)
         return applied, out, (None if tab is None else tab.permute(3, 0, 1, 2)), weights, ess, count
+
+    # -- cross-entropy update ---------------------------------------------------------------
+    def _cem_scalars(self, what, elites, S, gain, sigma_gain, sigma_min, sigma_max, tail):
+        """The host values of a cross-entropy update -> (E, gain, sigma_gain, sigma_min, sigma_max), checked."""
+        E = _count(what, "elites", elites)
+        if E > S:
+            raise ValueError(f"{what}: elites must be <= samples = {S}, got {E}")
+        step = lambda x: 0.0 < x <= 1.0
+        g, sg = _finite(what, "gain", gain, step, "in (0, 1]"), _finite(what, "sigma_gain", sigma_gain, step, "in (0, 1]")
+        lo = _finite(what, "sigma_min", sigma_min, _not_negative, ">= 0")
+        hi = _finite(what, "sigma_max", sigma_max, lambda x: x >= lo, f">= sigma_min = {lo}")
+        if tail not in cem.TAILS:
+            raise ValueError(f"{what}: tail must be 'hold' or 'zero', got {tail!r}")
+        return E, g, sg, lo, hi
+
+    def cem_update_into(self, returns, actions, nominal_in, sigma_in, nominal_out, var_out, sigma_out, *, samples: int, elites: int,
+                        gain: float = 1.0, sigma_gain: float = 1.0, sigma_min: float = 0.0, sigma_max: float = 1.0, shift: int = 1,
+                        tail: str = "hold", applied=None, table=None, lane_sigma=None, elite=None, threshold=None, count=None):
+        """Allocation-free cross-entropy update on tensors in the kernel's layouts (include/os2r_cem.h: os2rx_cem_update; the
+        arithmetic and its order are spelled out there).  With S = samples, E = elites, M robots, N = S M lanes (lane s M + m:
+        sample s of robot m) and K knots: returns [N], actions [K, N, 2], nominal_in [K, M, 2] and sigma_in [2, M] are read;
+        nominal_out [K, M, 2] (required, another tensor than nominal_in), var_out [K, M, 2] (required, the elite variance of every
+        knot and the workspace of the pooling), sigma_out [2, M] (required; may be sigma_in), applied [M, 2], table
+        [K, 2, D+1, N] (only its bias entries [:, :, D, :] are written), lane_sigma [2, N], elite [S, M] int32, threshold [M] and
+        count [M] int32 are written, each of the last six or None.  gain and sigma_gain in (0, 1], 0 <= sigma_min <= sigma_max,
+        shift in 0..K, tail "hold" or "zero".  Shapes, dtypes, device and contiguity are checked before the library is called (it
+        takes addresses)."""
+        what = "cem_update"
+        S, i32 = _count(what, "samples", samples), torch.int32
+        E, g, sg, lo, hi = self._cem_scalars(what, elites, S, gain, sigma_gain, sigma_min, sigma_max, tail)
+        K, N, M = self._mppi_lanes(what, actions, S)
+        _shift(what, shift, K)
+        if any(t is None for t in (returns, nominal_in, sigma_in, nominal_out, var_out, sigma_out)):
+            raise ValueError(f"{what}: returns, nominal_in, sigma_in, nominal_out, var_out and sigma_out are required")
+        self._outs(what, ((returns, (N,), None, "returns"), (actions, (K, N, 2), None, "actions"), (nominal_in, (K, M, 2), None, "nominal_in"),
+                          (sigma_in, (2, M), None, "sigma_in"), (nominal_out, (K, M, 2), None, "nominal_out"),
+                          (var_out, (K, M, 2), None, "var_out"), (sigma_out, (2, M), None, "sigma_out"), (applied, (M, 2), None, "applied"),
+                          (table, (K, 2, self.D + 1, N), None, "table"), (lane_sigma, (2, N), None, "lane_sigma"),
+                          (elite, (S, M), i32, "elite"), (threshold, (M,), None, "threshold"), (count, (M,), i32, "count")))
+        if nominal_out.data_ptr() == nominal_in.data_ptr():
+            raise ValueError(f"{what}: nominal_out must be another tensor than nominal_in (a knot is written into another slot than its own)")
+        if any(var_out.data_ptr() == t.data_ptr() for t in (returns, actions, nominal_in, sigma_in)):
+            raise ValueError(f"{what}: var_out must be a tensor of its own (the pooling reads it after every knot has written it)")
+        _call(cem, "os2rx_cem_update", "os2rx_last_error", C.byref(self._layout()), K, M, S, E, _ptr(returns), _ptr(actions), _ptr(nominal_in),
+              _ptr(sigma_in), g, sg, lo, hi, shift, cem.TAILS[tail], _ptr(nominal_out), _ptr(var_out), _ptr(sigma_out), _ptr(applied),
+              _ptr(table), _ptr(lane_sigma), _ptr(elite), _ptr(threshold), _ptr(count), self._stream())
+
+    def cem_update(self, returns, actions, nominal, sigma, *, samples: int, elites: int, gain: float = 1.0, sigma_gain: float = 1.0,
+                   sigma_min: float = 0.0, sigma_max: float = 1.0, shift: int = 1, tail: str = "hold", table=None,
+                   want_elite: bool = False, want_variance: bool = True):
+        """The cross-entropy update of M robots in one call (include/os2r_cem.h: os2rx_cem_update): with S = samples and N = S M
+        lanes, lane s M + m sample s of robot m -- a planner handle forked by copy_envs_from(real, arange(N) % M) --, returns [N]
+        and actions [K, N, 2] are what the noisy rollout_schedule(first_episode=True, want_actions=True) returned, nominal
+        [K, M, 2] the nominal its table held and sigma [M, 2] the width it sampled with.  Of every robot's lanes with a finite
+        return the best `elites` are kept (equal returns: the lower sample first); the nominal moves by `gain` towards the mean
+        of their action sequences and is clipped to [-1, 1], the width moves by `sigma_gain` towards their standard deviation
+        pooled over the knots and is clamped to [sigma_min, sigma_max]; a robot without a valid lane keeps both.  The nominal is
+        moved `shift` slots towards the present with the last slot held (tail="hold") or zeros behind it (tail="zero"): shift=0
+        between the iterations of one control step, shift=1 at its last.
+        table: None, True or an earlier call's table, as mppi_update takes it; only its bias entries are written.  sigma as an
+        earlier call returned it goes on without a copy.  The new nominal is written into one of two buffers the handle keeps
+        for this shape, the one `nominal` is not: feed it back and the two alternate.
+        -> (applied [M, 2]: knot 0 of the new mean, the action for real.step; nominal [K, M, 2]; table [N, K, 2, D+1] | None;
+        sigma [M, 2]; lane_sigma [N, 2]: sigma of every lane's robot, what rollout_schedule(sigma=...) takes without a copy;
+        var [K, M, 2] | None: the elite variance of every knot; elite [S, M] int32 | None: 1 for an elite lane; threshold [M]:
+        the lowest elite return; count [M] int32: the valid lanes of every robot).  sigma and lane_sigma are transposed views of
+        the [2, M] and [2, N] buffers the kernel wrote."""
+        what = "cem_update"
+        S = _count(what, "samples", samples)
+        self._cem_scalars(what, elites, S, gain, sigma_gain, sigma_min, sigma_max, tail)    # (here too: before anything is allocated)
+        K, N, M = self._mppi_lanes(what, actions, S)                      # (and these: they size what is allocated)
+        self._out(nominal, (K, M, 2), self.dtype, f"{what}: nominal")
+        if nominal is None or sigma is None:
+            raise ValueError(f"{what}: nominal and sigma are required")
+        sig_in = self._kernel_view(what, sigma, (M, 2), "sigma", (1, 0))
+        tab = self._planner_table(what, "_cem_tables", table, K, N)
+        out = self._other_buffer("_cem_nominals", (K, M, 2), nominal)
+        applied, var, sig, lane = self._new(M, 2), self._new(K, M, 2), self._new(2, M), self._new(2, N)
+        elite = self._new(S, M, dtype=torch.int32) if want_elite else None
+        threshold, count = self._new(M), self._new(M, dtype=torch.int32)
+        self.cem_update_into(returns, actions, nominal, sig_in, out, var, sig, samples=S, elites=elites, gain=gain, sigma_gain=sigma_gain,
+                             sigma_min=sigma_min, sigma_max=sigma_max, shift=shift, tail=tail, applied=applied, table=tab, lane_sigma=lane,
+                             elite=elite, threshold=threshold, count=count)
+        return (applied, out, (None if tab is None else tab.permute(3, 0, 1, 2)), sig.t(), lane.t(), var if want_variance else None, elite,
+                threshold, count)
 
     # -- particle-filter update -------------------------------------------------------------
     def _pf_lanes(self, what, obs, S):
