@@ -2,6 +2,7 @@
 """REINFORCE (Williams 1992) with a batch baseline for a linear-Gaussian policy on Monopod-balance-v1, entirely on the GPU.
 
   python examples/reinforce_balancing.py [--envs 8192] [--iters 20] [--horizon 500] [--step-size 0.05] [--sigma 0.2]
+                                         [--gradient torch|device] [--weight return|reward-to-go] [--gamma 1.0]
 
 The policy is a = clip(theta . [o; 1] + sigma * eps), eps ~ N(0, 1) per action and env-step.  Every iteration resets the batch and
 runs ONE os2r_rollout_policy_noisy call: all environments share theta, the noise is drawn inside the rollout kernel, and the
@@ -9,6 +10,11 @@ call returns the observations, the applied actions and the noise per step and th
 The score of step k is grad_theta log pi = eps / sigma * [o; 1] on the action components where the clip did not bind (where it
 did, the applied action does not depend on theta to first order and the step contributes nothing); the update is
 theta += step * mean_e[ (R_e - mean R) / std R * sum_k score_ek ] / mean episode length.  Nothing leaves the device.
+
+--gradient torch (the default) forms the update with five torch statements; --gradient device with one policy_gradient call
+(include/os2r_pg.h) on the arrays the rollout returned, as they are: reset -> rollout_policy -> policy_gradient -> theta +=.
+--weight reward-to-go (device only) weights every step with its discounted reward-to-go (--gamma) minus the batch's mean
+reward-to-go of that step, in place of the lane's normalised return.
 """
 import argparse
 import os
@@ -30,7 +36,12 @@ def main():
     ap.add_argument("--sigma", type=float, default=0.2, help="standard deviation of the exploration noise on both actions")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--dtype", default="f64", choices=["f64", "f32"])
+    ap.add_argument("--gradient", default="torch", choices=["torch", "device"], help="the update: five torch statements, or one policy_gradient call")
+    ap.add_argument("--weight", default="return", choices=["return", "reward-to-go"], help="what weights a step's score (reward-to-go: device only)")
+    ap.add_argument("--gamma", type=float, default=1.0, help="the discount of the reward-to-go")
     args = ap.parse_args()
+    if args.weight == "reward-to-go" and args.gradient != "device":
+        ap.error("--weight reward-to-go needs --gradient device")
     N, H = args.envs, args.horizon
     env = g.make("Monopod-balance-v1", num_envs=N, seed=args.seed, dtype=args.dtype)
     env.reset()
@@ -42,6 +53,25 @@ def main():
     t0 = time.time()
     for it in range(args.iters):
         obs0 = sim.reset()
+        if args.gradient == "device":
+            ret, length, (O, R, Dn, _, _), (A, E) = sim.rollout_policy(H, theta, sigma=sigma, salt=it, first_episode=True,
+                                                                       want_outputs=True, want_actions=True, want_noise=True)
+            if args.weight == "return":
+                weight = dict(adv=(ret - ret.mean()) / ret.std().clamp_min(1e-8))                  # batch baseline
+            else:
+                # the baseline of step k is the batch's mean discounted reward from k on, from the per-step means (an episode that
+                # has ended counts as 0 from there on)
+                counted = (torch.arange(H, device=dev).unsqueeze(1) < length.unsqueeze(0)).to(dt)
+                ahead = torch.arange(H, device=dev).unsqueeze(0) - torch.arange(H, device=dev).unsqueeze(1)      # [k, i]: i - k
+                discount = torch.triu(torch.full((H, H), args.gamma, dtype=dt, device=dev) ** ahead.clamp_min(0))
+                base = (discount @ (R * counted).mean(1)).unsqueeze(1)                               # [H, 1]
+                weight = dict(rewards=R, done=Dn, gamma=args.gamma, baseline=base)
+            grad, steps, clipped, valid, _, _, _ = sim.policy_gradient(O, E, sigma, obs0=obs0, actions=A, length=length, **weight)
+            mean_len = float(steps[0]) / max(int(valid[0]), 1)
+            theta = theta + args.step_size * grad[0] / float(max(int(steps[0]), 1))
+            print(f"iteration {it}: mean return {float(ret.mean()):8.2f}  best {float(ret.max()):6.1f}  "
+                  f"mean episode length {mean_len:6.1f}  clipped {100 * float(clipped.sum()) / float(max(2 * int(steps[0]), 1)):4.1f} %", flush=True)
+            continue
         # (the salt separates the iterations' noise: every rollout starts at another step counter anyway, the salt makes it explicit)
         ret, length, (O, _, Dn, _, _), (A, E) = sim.rollout_policy(H, theta, sigma=sigma, salt=it, first_episode=True,
                                                                    want_outputs=True, want_actions=True, want_noise=True)
@@ -59,6 +89,7 @@ def main():
     wall = time.time() - t0
     steps = args.iters * N * H
     print(f"{steps / 1e6:.1f} M env-steps in {wall:.2f} s ({steps / wall / 1e6:.1f} M env-steps/s incl. resets and updates)")
+    print(f"gradient {args.gradient}, weight {args.weight}: torch's peak allocated memory {torch.cuda.max_memory_allocated(dev) / 1e6:.0f} MB")
     env.close()
 
 

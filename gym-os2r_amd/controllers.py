@@ -1,5 +1,6 @@
 """The controller calls of a HipSim: LQR gains, the iLQR backward pass, its line search with and without a steered mu, the MPPI
-update, the cross-entropy update, the particle-filter update, the Kalman filter update and the two calls of the unscented Kalman filter (its sigma points and its update), each as an allocation-free ``*_into`` on tensors in the kernel's layout and an allocating
+update, the cross-entropy update, the particle-filter update, the Kalman filter update, the two calls of the unscented Kalman filter (its sigma points and its update) and the
+score-function policy gradient, each as an allocation-free ``*_into`` on tensors in the kernel's layout and an allocating
 wrapper around it.  ``Controllers`` is the plain base class HipSim (gym_os2r_amd.sim) inherits them from; it uses the handle's
 ``_out``, ``_in``, ``_new``, ``_layout``, ``_stream`` and ``_check``.
 
@@ -14,7 +15,7 @@ import math
 
 import torch
 
-from . import abi, cem, control, ekf, mppi, pf, search, steer, ukf
+from . import abi, cem, control, ekf, mppi, pf, pg, search, steer, ukf
 from ._lib import Os2rError, _ptr
 
 NOMINAL_KEYS = ("cost", "actions", "obs", "end_obs", "lx", "lu", "p_final")
@@ -949,3 +950,115 @@ class Controllers:
         self.ukf_update_into((q, qd), p_in, meas, prec, x_out, p_out, Q=Q, done=done, gate=gate, alpha=alpha, beta=beta, kappa=kappa, nis=nis,
                              used=used, refused=refused, innov=innov, lost=lost, points_out=points, failed=failed)
         return x_out, p_out.permute(2, 0, 1), nis, used, refused, innov, lost, points, failed
+
+    # -- score-function policy gradient -----------------------------------------------------
+    def _pg_lanes(self, what, obs, policies):
+        """obs [K, S P, D] of a policy gradient with P = policies -> (K, N = S P, S, P), checked."""
+        P = _count(what, "policies", policies)
+        if not isinstance(obs, torch.Tensor) or obs.dim() != 3:
+            raise ValueError(f"{what}: obs must be a tensor of shape (K, samples * policies, {self.D})")
+        K, N = int(obs.shape[0]), int(obs.shape[1])
+        if not 1 <= K <= 65535:
+            raise ValueError(f"{what}: obs must hold 1..65535 steps, got {K}")
+        S = _split(what, N, P, f"obs [{K} steps]", "policies")
+        if N > 2 ** 31 - 1 or S * K > 2 ** 31 - 1:
+            raise ValueError(f"{what}: {N} lanes, or {S} samples of {K} steps, exceed what an int32 holds")
+        return K, N, S, P
+
+    def _pg_weight(self, what, adv, rewards, done, gamma, baseline, rtg):
+        """The two ways a policy gradient is given its weight -> gamma as a float, checked: adv or rewards, not both; rewards with
+        done; baseline and the reward-to-go with rewards only."""
+        if (adv is None) == (rewards is None):
+            raise ValueError(f"{what}: the weight is adv (one number per lane) or rewards (with done), one or the other")
+        if rewards is not None and done is None:
+            raise ValueError(f"{what}: rewards need done (an episode's end cuts the reward-to-go)")
+        if rewards is None and (baseline is not None or rtg):
+            raise ValueError(f"{what}: baseline and the reward-to-go need rewards")
+        return _finite(what, "gamma", math.nan if isinstance(gamma, bool) else gamma, lambda x: 0.0 <= x <= 1.0, "in [0, 1]", repr(gamma))
+
+    def policy_gradient_into(self, obs, noise, sigma, grad, lane_grad, lane_count, *, policies: int = 1, obs0=None, actions=None,
+                             tanh: bool = False, length=None, adv=None, rewards=None, done=None, gamma: float = 1.0, baseline=None,
+                             lsig_grad=None, lane_lsig=None, steps=None, clipped=None, valid=None, rtg=None):
+        """Allocation-free policy gradient on tensors in the kernel's layouts (include/os2r_pg.h: os2rg_policy_gradient; the
+        arithmetic and its order are spelled out there).  With P = policies, S samples, N = S P lanes (lane s P + p: sample s of
+        policy p) and K steps: obs [K, N, D], obs0 [N, D] (None: obs[k] is what step k's action saw), noise [K, N, 2], actions
+        [K, N, 2] (required unless tanh), sigma [2] or [2, N], length [N] int32 (None: K) and the weight -- adv [N], or rewards
+        [K, N] with done [K, N] uint8, gamma in [0, 1] and baseline [K, P] or None -- are read; grad [2, D+1, P], lane_grad
+        [2, D+1, N] and lane_count [4, N] int32 (all three required), lsig_grad [2, P] with lane_lsig [2, N], steps [P] int32,
+        clipped [2, P] int32, valid [P] int32 and rtg [K, N] (with rewards) are written, each of the last six or None.  Shapes,
+        dtypes, device, contiguity, alignment and overlap are checked before the library is called (it takes addresses)."""
+        what = "policy_gradient"
+        K, N, S, P = self._pg_lanes(what, obs, policies)
+        g = self._pg_weight(what, adv, rewards, done, gamma, baseline, rtg is not None)
+        D, i32 = self.D, torch.int32
+        if any(t is None for t in (noise, sigma, grad, lane_grad, lane_count)):
+            raise ValueError(f"{what}: obs, noise, sigma, grad, lane_grad and lane_count are required")
+        if not tanh and actions is None:
+            raise ValueError(f"{what}: actions are required unless tanh (where the clip bound, a step adds nothing)")
+        if (lsig_grad is None) != (lane_lsig is None):
+            raise ValueError(f"{what}: lsig_grad and lane_lsig go together (the second launch reads the one to write the other)")
+        if tanh:
+            actions = None
+        if rewards is None:
+            done = None
+        per_lane = isinstance(sigma, torch.Tensor) and sigma.dim() == 2
+        inputs = ((obs, (K, N, D), None, "obs"), (obs0, (N, D), None, "obs0"), (noise, (K, N, 2), None, "noise"),
+                  (actions, (K, N, 2), None, "actions"), (sigma, (2, N) if per_lane else (2,), None, "sigma"), (length, (N,), i32, "length"),
+                  (adv, (N,), None, "adv"), (rewards, (K, N), None, "rewards"), (done, (K, N), torch.uint8, "done"),
+                  (baseline, (K, P), None, "baseline"))
+        outputs = ((grad, (2, D + 1, P), None, "grad"), (lane_grad, (2, D + 1, N), None, "lane_grad"), (lsig_grad, (2, P), None, "lsig_grad"),
+                   (lane_lsig, (2, N), None, "lane_lsig"), (steps, (P,), i32, "steps"), (clipped, (2, P), i32, "clipped"),
+                   (valid, (P,), i32, "valid"), (rtg, (K, N), None, "rtg"), (lane_count, (pg.LANE_COUNTS, N), i32, "lane_count"))
+        self._outs(what, inputs + outputs)
+        for t, name in ((noise, "noise"), (actions, "actions")):
+            if t is not None and t.data_ptr() % (2 * t.element_size()):
+                raise ValueError(f"{what}: {name} must be aligned to a pair of its elements")
+        spans = [(name, t.data_ptr(), t.data_ptr() + t.numel() * t.element_size()) for t, _, _, name in inputs + outputs if t is not None]
+        first_output = sum(t is not None for t, _, _, _ in inputs)
+        for o in range(first_output, len(spans)):         # every output against every input and every output before it
+            name, lo, hi = spans[o]
+            for other, lo2, hi2 in spans[:o]:
+                if lo < hi2 and lo2 < hi:
+                    raise ValueError(f"{what}: {name} overlaps {other} (an output shares no memory with an input or another output)")
+        _call(pg, "os2rg_policy_gradient", "os2rg_last_error", C.byref(self._layout()), K, P, S,
+              (pg.TANH if tanh else 0) | (pg.SIGMA_PER_LANE if per_lane else 0), _ptr(obs), _ptr(obs0), _ptr(noise), _ptr(actions), _ptr(sigma),
+              _ptr(length), _ptr(adv), _ptr(rewards), _ptr(done), g, _ptr(baseline), _ptr(grad), _ptr(lane_grad), _ptr(lsig_grad),
+              _ptr(lane_lsig), _ptr(steps), _ptr(clipped), _ptr(valid), _ptr(rtg), _ptr(lane_count), self._stream())
+
+    def policy_gradient(self, obs, noise, sigma, *, policies: int = 1, obs0=None, actions=None, tanh: bool = False, length=None, adv=None,
+                        rewards=None, done=None, gamma: float = 1.0, baseline=None, want_log_sigma: bool = False, want_lane: bool = False,
+                        want_rtg: bool = False):
+        """The score-function (REINFORCE) gradient of P = policies linear-Gaussian policies in one call (include/os2r_pg.h:
+        os2rg_policy_gradient): with S samples and N = S P lanes, lane s P + p sample s of policy p -- the order
+        copy_envs_from(real, arange(N) % P) forks in --, obs [K, N, D], actions [K, N, 2], noise [K, N, 2] and length [N] are what
+        the noisy rollout_policy(first_episode=True, want_outputs=True, want_actions=True, want_noise=True) returned and sigma (a
+        float, [2] or [N, 2]) what it sampled with; all are taken without a copy.  obs0 [N, D]: what reset() or the previous
+        window's last step returned, the observation step 0 saw; None with obs the knot observations of a recorded rollout
+        (want_knot_obs), which already are what every step saw.  Step k of a lane counts while k < length; its score is
+        eps / sigma [x; 1] on the action components where sigma > 0 and -- unless tanh -- the clip did not bind.  The weight of
+        a step is adv [N], one number per lane, or the discounted reward-to-go of rewards [K, N] cut at done [K, N] with gamma
+        in [0, 1], minus baseline [K, P] where given.  A lane one of whose sums is not finite is left out of its policy's sums.
+        -> (grad [P, 2, D+1]: the sum over the policy's valid lanes, a permuted view of the kernel's layout -- with P = N what
+        rollout_policy takes as per-environment weights without a copy; steps [P] int32: the counted steps; clipped [P, 2]
+        int32: how often the clip bound; valid [P] int32: the valid lanes; lsig_grad [P, 2] | None: the gradient with respect to
+        log sigma; lane_grad [N, 2, D+1] | None: the per-lane sums; rtg [K, N] | None: the reward-to-go)."""
+        what = "policy_gradient"
+        K, N, S, P = self._pg_lanes(what, obs, policies)                    # (here too, all: they size what is allocated)
+        self._pg_weight(what, adv, rewards, done, gamma, baseline, want_rtg)
+        if isinstance(sigma, bool) or sigma is None:
+            raise ValueError(f"{what}: sigma must be a float, a [2] tensor or an [{N}, 2] tensor, got {sigma!r}")
+        if isinstance(sigma, (int, float)):
+            sigma = torch.full((2,), float(sigma), dtype=self.dtype, device=self.device)
+        elif isinstance(sigma, torch.Tensor) and sigma.dim() == 2:
+            sigma = self._kernel_view(what, sigma, (N, 2), "sigma", (1, 0))  # the [2, N] an [N, 2] sigma is a view of goes on as it is
+        D, i32 = self.D, torch.int32
+        grad, lane, count = self._new(2, D + 1, P), self._new(2, D + 1, N), self._new(pg.LANE_COUNTS, N, dtype=i32)
+        steps, clipped, valid = self._new(P, dtype=i32), self._new(2, P, dtype=i32), self._new(P, dtype=i32)
+        lsig = self._new(2, P) if want_log_sigma else None
+        lane_lsig = self._new(2, N) if want_log_sigma else None
+        rtg = self._new(K, N) if want_rtg else None
+        self.policy_gradient_into(obs, noise, sigma, grad, lane, count, policies=P, obs0=obs0, actions=actions, tanh=tanh, length=length,
+                                  adv=adv, rewards=rewards, done=done, gamma=gamma, baseline=baseline, lsig_grad=lsig, lane_lsig=lane_lsig,
+                                  steps=steps, clipped=clipped, valid=valid, rtg=rtg)
+        return (grad.permute(2, 0, 1), steps, clipped.t(), valid, None if lsig is None else lsig.t(),
+                lane.permute(2, 0, 1) if want_lane else None, rtg)

@@ -1,0 +1,26 @@
+// os2r_pg_inst.hip — the three os2rg_policy_gradient kernels (os2r_pg.hpp) of one dtype; compiled once per OS2R_REAL into
+// libos2r_pg.so.  They need no robot constants and no chain length.
+#include "os2r_pg.hpp"
+
+#ifndef OS2R_REAL
+#error "OS2R_REAL must be float or double"
+#endif
+
+namespace os2r {
+
+using T = OS2R_REAL;
+
+// the sums of every lane, then -- behind them on the same stream -- the sums over the samples of every policy, which read what
+// the first launch wrote into lane_grad, lane_lsig and lane_count: a wave per total above 64 samples, a thread per total up to 64
+template <>
+void launch_policy_gradient<T>(const PgArgs<T>& p, hipStream_t s) {
+  const unsigned entries = (unsigned)(2 * (p.D + 1) + 2 + kPgIntegerSums);
+  const unsigned lane_groups = (unsigned)((p.N * kPgThreads + kPgBlock - 1) / kPgBlock);
+  hipLaunchKernelGGL((policy_gradient_lane_kernel<T>), dim3(lane_groups), dim3(kPgBlock), 0, s, p);
+  if (p.S > kPgChunks)
+    hipLaunchKernelGGL((policy_gradient_sum_kernel<T>), dim3((unsigned)p.P, entries), dim3(kPgChunks), 0, s, p);
+  else
+    hipLaunchKernelGGL((policy_gradient_sum_few_kernel<T>), dim3((unsigned)((p.P + kPgBlock - 1) / kPgBlock), entries), dim3(kPgBlock), 0, s, p);
+}
+
+}  // namespace os2r
