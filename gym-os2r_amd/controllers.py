@@ -1,6 +1,6 @@
 """The controller calls of a HipSim: LQR gains, the iLQR backward pass, its line search with and without a steered mu, the MPPI
-update, the cross-entropy update, the particle-filter update, the Kalman filter update, the two calls of the unscented Kalman filter (its sigma points and its update) and the
-score-function policy gradient, each as an allocation-free ``*_into`` on tensors in the kernel's layout and an allocating
+update, the cross-entropy update, the particle-filter update, the Kalman filter update, the two calls of the unscented Kalman filter (its sigma points and its update), the
+score-function policy gradient and the two calls of the critic (GAE(lambda) and the linear value fit), each as an allocation-free ``*_into`` on tensors in the kernel's layout and an allocating
 wrapper around it.  ``Controllers`` is the plain base class HipSim (gym_os2r_amd.sim) inherits them from; it uses the handle's
 ``_out``, ``_in``, ``_new``, ``_layout``, ``_stream`` and ``_check``.
 
@@ -15,7 +15,7 @@ import math
 
 import torch
 
-from . import abi, cem, control, ekf, mppi, pf, pg, search, steer, ukf
+from . import abi, cem, control, critic, ekf, mppi, pf, pg, search, steer, ukf
 from ._lib import Os2rError, _ptr
 
 NOMINAL_KEYS = ("cost", "actions", "obs", "end_obs", "lx", "lu", "p_final")
@@ -1062,3 +1062,106 @@ class Controllers:
                                   steps=steps, clipped=clipped, valid=valid, rtg=rtg)
         return (grad.permute(2, 0, 1), steps, clipped.t(), valid, None if lsig is None else lsig.t(),
                 lane.permute(2, 0, 1) if want_lane else None, rtg)
+
+    # -- the critic: GAE(lambda) and the linear value fit -----------------------------------
+    def _no_overlap(self, what, inputs, outputs):
+        """No output of `outputs` shares memory with a row of `inputs` or with an output before it (rows as _outs takes them)."""
+        spans = [(name, t.data_ptr(), t.data_ptr() + t.numel() * t.element_size()) for t, _, _, name in inputs + outputs if t is not None]
+        first_output = sum(t is not None for t, _, _, _ in inputs)
+        for o in range(first_output, len(spans)):
+            name, lo, hi = spans[o]
+            for other, lo2, hi2 in spans[:o]:
+                if lo < hi2 and lo2 < hi:
+                    raise ValueError(f"{what}: {name} overlaps {other} (an output shares no memory with an input or another output)")
+
+    def gae_into(self, obs, rewards, done, value_w, adv, values, *, obs0, policies: int = 1, term_obs=None, length=None,
+                 gamma: float = 0.99, lam: float = 0.95, ret=None):
+        """Allocation-free GAE(lambda) on tensors in the kernel's layouts (include/os2r_critic.h: os2rv_gae; the arithmetic and
+        its order are spelled out there).  With P = policies, S samples, N = S P lanes (lane s P + p: sample s of policy p) and K
+        steps: obs [K, N, D], obs0 [N, D] (required: what step 0 saw), term_obs [K, N, D] or None, rewards [K, N], done [K, N]
+        uint8, length [N] int32 (None: K) and value_w [D+1, P] are read; adv [K, N] and values [K, N] (both required: the second
+        launch reads values) and ret [K, N] (or None) are written.  gamma and lam in [0, 1].  Shapes, dtypes, device, contiguity
+        and overlap are checked before the library is called (it takes addresses)."""
+        what = "gae"
+        K, N, S, P = self._pg_lanes(what, obs, policies)
+        unit = lambda x: 0.0 <= x <= 1.0
+        g = _finite(what, "gamma", math.nan if isinstance(gamma, bool) else gamma, unit, "in [0, 1]", repr(gamma))
+        lm = _finite(what, "lam", math.nan if isinstance(lam, bool) else lam, unit, "in [0, 1]", repr(lam))
+        if any(t is None for t in (obs0, rewards, done, value_w, adv, values)):
+            raise ValueError(f"{what}: obs, obs0, rewards, done, value_w, adv and values are required")
+        D = self.D
+        inputs = ((obs, (K, N, D), None, "obs"), (obs0, (N, D), None, "obs0"), (term_obs, (K, N, D), None, "term_obs"),
+                  (rewards, (K, N), None, "rewards"), (done, (K, N), torch.uint8, "done"), (length, (N,), torch.int32, "length"),
+                  (value_w, (D + 1, P), None, "value_w"))
+        outputs = ((adv, (K, N), None, "adv"), (ret, (K, N), None, "ret"), (values, (K, N), None, "values"))
+        self._outs(what, inputs + outputs)
+        self._no_overlap(what, inputs, outputs)
+        _call(critic, "os2rv_gae", "os2rv_last_error", C.byref(self._layout()), K, P, S, _ptr(obs), _ptr(obs0), _ptr(term_obs), _ptr(rewards),
+              _ptr(done), _ptr(length), _ptr(value_w), g, lm, _ptr(adv), _ptr(ret), _ptr(values), self._stream())
+
+    def gae(self, obs, rewards, done, value_w, *, obs0, policies: int = 1, term_obs=None, length=None, gamma: float = 0.99,
+            lam: float = 0.95, want_returns: bool = True, want_values: bool = False):
+        """The generalised advantage estimate of every step of every lane under a linear value function per policy, in one call
+        (include/os2r_critic.h: os2rv_gae): obs [K, N, D], rewards [K, N], done [K, N] uint8 and term_obs [K, N, D] are what
+        rollout_policy(want_outputs=True) returned, all taken without a copy; obs0 [N, D] what reset() or the previous window's
+        last step returned; value_w [P, D+1] the weights of V_p(x) = w_p . [x; 1] as value_fit returns them (a permuted view of
+        the kernel's [D+1, P] goes on without a copy).  A done step (bit 0) or a guarded one (bit 2) ends its episode with value
+        0 behind it, a TimeLimit truncation (bit 1 alone) with the value of term_obs (0 without term_obs); the window counts
+        whole, across auto-resets, or up to length [N] int32 where given.
+        -> (adv [K, N]; ret [K, N] | None: adv + values, the target of value_fit; values [K, N] | None), 0 where k >= length.
+        policy_gradient(rewards=adv, done=done, gamma=0.0) weights every step with its advantage."""
+        what = "gae"
+        K, N, S, P = self._pg_lanes(what, obs, policies)                    # (here too: they size what is allocated)
+        w = self._kernel_view(what, value_w, (P, self.D + 1), "value_w", (1, 0))
+        adv, values = self._new(K, N), self._new(K, N)
+        ret = self._new(K, N) if want_returns else None
+        self.gae_into(obs, rewards, done, w, adv, values, obs0=obs0, policies=P, term_obs=term_obs, length=length, gamma=gamma, lam=lam,
+                      ret=ret)
+        return adv, ret, values if want_values else None
+
+    def value_fit_into(self, obs, target, w, lane_mom, mom, lane_count, *, obs0, policies: int = 1, length=None, prev=None,
+                       ridge: float = 0.0, failed=None, steps=None, valid=None):
+        """Allocation-free ridge least-squares fit of the value weights on tensors in the kernel's layouts (include/os2r_critic.h:
+        os2rv_value_fit; the arithmetic and its order are spelled out there).  With P = policies, N = S P lanes, K steps and
+        E = gym_os2r_amd.critic.moments(D): obs [K, N, D], obs0 [N, D] (required), target [K, N], length [N] int32 (None: K) and
+        prev [D+1, P] (None: the ridge pulls towards 0) are read; w [D+1, P], lane_mom [E, N], mom [E, P] and lane_count [2, N]
+        int32 (all four required: each launch reads what the one before it wrote) and failed, steps, valid [P] int32 (each or
+        None) are written.  ridge >= 0.  Shapes, dtypes, device, contiguity and overlap are checked before the library is called
+        (it takes addresses)."""
+        what = "value_fit"
+        K, N, S, P = self._pg_lanes(what, obs, policies)
+        r = _finite(what, "ridge", math.nan if isinstance(ridge, bool) else ridge, _not_negative, ">= 0", repr(ridge))
+        if any(t is None for t in (obs0, target, w, lane_mom, mom, lane_count)):
+            raise ValueError(f"{what}: obs, obs0, target, w, lane_mom, mom and lane_count are required")
+        D, i32 = self.D, torch.int32
+        E = critic.moments(D)
+        inputs = ((obs, (K, N, D), None, "obs"), (obs0, (N, D), None, "obs0"), (target, (K, N), None, "target"),
+                  (length, (N,), i32, "length"), (prev, (D + 1, P), None, "prev"))
+        outputs = ((w, (D + 1, P), None, "w"), (lane_mom, (E, N), None, "lane_mom"), (mom, (E, P), None, "mom"),
+                   (lane_count, (critic.LANE_COUNTS, N), i32, "lane_count"), (failed, (P,), i32, "failed"), (steps, (P,), i32, "steps"),
+                   (valid, (P,), i32, "valid"))
+        self._outs(what, inputs + outputs)
+        self._no_overlap(what, inputs, outputs)
+        _call(critic, "os2rv_value_fit", "os2rv_last_error", C.byref(self._layout()), K, P, S, _ptr(obs), _ptr(obs0), _ptr(target),
+              _ptr(length), _ptr(prev), r, _ptr(w), _ptr(lane_mom), _ptr(mom), _ptr(lane_count), _ptr(failed), _ptr(steps), _ptr(valid),
+              self._stream())
+
+    def value_fit(self, obs, target, *, obs0, policies: int = 1, length=None, prev=None, ridge: float = 0.0):
+        """The ridge least-squares refit of P = policies linear value functions on the batch in one call (include/os2r_critic.h:
+        os2rv_value_fit): w_p minimises sum (w . [x_k; 1] - target[k][l])^2 + ridge |w - prev_p|^2 over the counted steps of the
+        policy's valid lanes, by the normal equations and a Cholesky factor.  obs [K, N, D] and obs0 [N, D] as in gae(), target
+        [K, N] the ret of gae() or the rtg of policy_gradient(), prev [P, D+1] the weights an earlier call returned (None: 0).
+        A lane one of whose moment sums is not finite is left out.
+        -> (w [P, D+1]: a permuted view of the kernel's layout, what gae() and the next value_fit(prev=...) take without a copy
+        -- where the factor failed, prev (or 0); failed [P] int32: 0, or j + 1 where the factor failed at column j; steps [P]
+        int32: the counted steps; valid [P] int32: the valid lanes)."""
+        what = "value_fit"
+        K, N, S, P = self._pg_lanes(what, obs, policies)                    # (here too: they size what is allocated)
+        D, i32 = self.D, torch.int32
+        pv = self._kernel_view(what, prev, (P, D + 1), "prev", (1, 0))
+        E = critic.moments(D)
+        w, lane_mom, mom, count = self._new(D + 1, P), self._new(E, N), self._new(E, P), self._new(critic.LANE_COUNTS, N, dtype=i32)
+        failed, steps, valid = (self._new(P, dtype=i32) for _ in range(3))
+        self.value_fit_into(obs, target, w, lane_mom, mom, count, obs0=obs0, policies=P, length=length, prev=pv, ridge=ridge, failed=failed,
+                            steps=steps, valid=valid)
+        return w.t(), failed, steps, valid
