@@ -1,6 +1,6 @@
 """The controller calls of a HipSim: LQR gains, the iLQR backward pass, its line search with and without a steered mu, the MPPI
 update, the cross-entropy update, the particle-filter update, the Kalman filter update, the two calls of the unscented Kalman filter (its sigma points and its update), the
-score-function policy gradient and the two calls of the critic (GAE(lambda) and the linear value fit), each as an allocation-free ``*_into`` on tensors in the kernel's layout and an allocating
+score-function policy gradient, the two calls of the critic (GAE(lambda) and the linear value fit) and the clipped-surrogate (PPO) gradient, each as an allocation-free ``*_into`` on tensors in the kernel's layout and an allocating
 wrapper around it.  ``Controllers`` is the plain base class HipSim (gym_os2r_amd.sim) inherits them from; it uses the handle's
 ``_out``, ``_in``, ``_new``, ``_layout``, ``_stream`` and ``_check``.
 
@@ -15,7 +15,7 @@ import math
 
 import torch
 
-from . import abi, cem, control, critic, ekf, mppi, pf, pg, search, steer, ukf
+from . import abi, cem, control, critic, ekf, mppi, pf, pg, ppo, search, steer, ukf
 from ._lib import Os2rError, _ptr
 
 NOMINAL_KEYS = ("cost", "actions", "obs", "end_obs", "lx", "lu", "p_final")
@@ -1165,3 +1165,94 @@ class Controllers:
         self.value_fit_into(obs, target, w, lane_mom, mom, count, obs0=obs0, policies=P, length=length, prev=pv, ridge=ridge, failed=failed,
                             steps=steps, valid=valid)
         return w.t(), failed, steps, valid
+
+    # -- the clipped-surrogate (PPO) gradient -----------------------------------------------
+    def ppo_gradient_into(self, obs, noise, sigma, weights, weights_old, adv, grad, lane_grad, lane_stat, lane_count, *, policies: int = 1,
+                          clip: float = 0.2, obs0=None, actions=None, tanh: bool = False, length=None, sigma_new=None, lsig_grad=None,
+                          lane_lsig=None, stat=None, steps=None, clipped=None, gated=None, valid=None, ratio=None):
+        """Allocation-free clipped-surrogate gradient on tensors in the kernel's layouts (include/os2r_ppo.h: os2ro_ppo_gradient;
+        the arithmetic and its order are spelled out there).  With P = policies, S samples, N = S P lanes (lane s P + p: sample s
+        of policy p) and K steps: obs [K, N, D], obs0 [N, D] (None: obs[k] is what step k's action saw), noise [K, N, 2], actions
+        [K, N, 2] (required unless tanh), sigma [2] or [2, N] (the width the batch was sampled with), sigma_new [2, P] (None: the
+        same width), weights and weights_old [2, D+1, P] (evaluated, and sampled with), length [N] int32 (None: K) and adv [K, N]
+        are read, clip in (0, 1); grad [2, D+1, P], lane_grad [2, D+1, N], lane_stat [3, N] and lane_count [5, N] int32 (all four
+        required), lsig_grad [2, P] with lane_lsig [2, N], stat [3, P], steps [P] int32, clipped [2, P] int32, gated [P] int32,
+        valid [P] int32 and ratio [K, N] are written, each of the last eight or None.  Shapes, dtypes, device, contiguity,
+        alignment and overlap are checked before the library is called (it takes addresses)."""
+        what = "ppo_gradient"
+        K, N, S, P = self._pg_lanes(what, obs, policies)
+        c = _finite(what, "clip", math.nan if isinstance(clip, bool) else clip, lambda x: 0.0 < x < 1.0, "in (0, 1)", repr(clip))
+        D, i32 = self.D, torch.int32
+        if any(t is None for t in (noise, sigma, weights, weights_old, adv, grad, lane_grad, lane_stat, lane_count)):
+            raise ValueError(f"{what}: obs, noise, sigma, weights, weights_old, adv, grad, lane_grad, lane_stat and lane_count are required")
+        if not tanh and actions is None:
+            raise ValueError(f"{what}: actions are required unless tanh (where the clip bound, a step's component is left out)")
+        if (lsig_grad is None) != (lane_lsig is None):
+            raise ValueError(f"{what}: lsig_grad and lane_lsig go together (the second launch reads the one to write the other)")
+        if tanh:
+            actions = None
+        per_lane = isinstance(sigma, torch.Tensor) and sigma.dim() == 2
+        inputs = ((obs, (K, N, D), None, "obs"), (obs0, (N, D), None, "obs0"), (noise, (K, N, 2), None, "noise"),
+                  (actions, (K, N, 2), None, "actions"), (sigma, (2, N) if per_lane else (2,), None, "sigma"),
+                  (sigma_new, (2, P), None, "sigma_new"), (weights, (2, D + 1, P), None, "weights"),
+                  (weights_old, (2, D + 1, P), None, "weights_old"), (length, (N,), i32, "length"), (adv, (K, N), None, "adv"))
+        outputs = ((grad, (2, D + 1, P), None, "grad"), (lane_grad, (2, D + 1, N), None, "lane_grad"), (lsig_grad, (2, P), None, "lsig_grad"),
+                   (lane_lsig, (2, N), None, "lane_lsig"), (stat, (ppo.STATS, P), None, "stat"), (lane_stat, (ppo.STATS, N), None, "lane_stat"),
+                   (steps, (P,), i32, "steps"), (clipped, (2, P), i32, "clipped"), (gated, (P,), i32, "gated"), (valid, (P,), i32, "valid"),
+                   (ratio, (K, N), None, "ratio"), (lane_count, (ppo.LANE_COUNTS, N), i32, "lane_count"))
+        self._outs(what, inputs + outputs)
+        for t, name in ((noise, "noise"), (actions, "actions")):
+            if t is not None and t.data_ptr() % (2 * t.element_size()):
+                raise ValueError(f"{what}: {name} must be aligned to a pair of its elements")
+        self._no_overlap(what, inputs, outputs)
+        _call(ppo, "os2ro_ppo_gradient", "os2ro_last_error", C.byref(self._layout()), K, P, S,
+              (ppo.TANH if tanh else 0) | (ppo.SIGMA_PER_LANE if per_lane else 0), _ptr(obs), _ptr(obs0), _ptr(noise), _ptr(actions), _ptr(sigma),
+              _ptr(sigma_new), _ptr(weights), _ptr(weights_old), _ptr(length), _ptr(adv), c, _ptr(grad), _ptr(lane_grad), _ptr(lsig_grad),
+              _ptr(lane_lsig), _ptr(stat), _ptr(lane_stat), _ptr(steps), _ptr(clipped), _ptr(gated), _ptr(valid), _ptr(ratio), _ptr(lane_count),
+              self._stream())
+
+    def ppo_gradient(self, obs, noise, sigma, weights, weights_old, adv, *, policies: int = 1, clip: float = 0.2, obs0=None, actions=None,
+                     tanh: bool = False, length=None, sigma_new=None, want_log_sigma: bool = False, want_lane: bool = False,
+                     want_ratio: bool = False):
+        """The gradient of PPO's clipped surrogate sum min(rho psi, clamp(rho, 1 - clip, 1 + clip) psi) of P = policies
+        linear-Gaussian policies in one call (include/os2r_ppo.h: os2ro_ppo_gradient), evaluated at `weights` on a batch that was
+        sampled with `weights_old`: obs, noise, actions, length, obs0, sigma (a float, [2] or [N, 2]) and tanh are those of
+        policy_gradient, all taken without a copy; adv [K, N] is the weight psi of every step as gae() returned it (normalised
+        or not).  weights and weights_old are [P, 2, D+1] -- a permuted view of the kernel's [2, D+1, P], as this call's grad
+        is, goes on without a copy --, sigma_new [P, 2] the width of the policy being evaluated (None: the width of the batch).
+        rho is the likelihood ratio of the pre-squash sample over the components on which the action clip did not bind; a
+        step adds its gradient unless (psi > 0 and rho > 1 + clip) or (psi < 0 and rho < 1 - clip).  With weights equal to
+        weights_old and sigma_new None every rho is 1 and the call returns the bits of policy_gradient(rewards=adv, gamma=0.0).
+        A lane one of whose sums is not finite is left out of its policy's sums.
+        -> (grad [P, 2, D+1]: a permuted view of the kernel's layout; stats [P, 3]: the sums of the surrogate itself, of rho - 1
+        (dev) and of log rho before the widths' factor (logr) -- where the widths are unchanged (dev - logr) / steps is the k3
+        estimate of the KL divergence KL(old || new), mean((rho - 1) - log rho) over the counted steps, and -logr / steps the
+        k1 estimate; steps [P] int32: the counted steps; clipped [P, 2] int32: how often the action clip bound; gated [P] int32:
+        the steps whose gradient the ratio's clip took out; valid [P] int32: the valid lanes; lsig_grad [P, 2] | None: the
+        gradient with respect to the log of the evaluated width; lane_grad [N, 2, D+1] | None: the per-lane sums; ratio [K, N] |
+        None: rho of every counted step, 0 behind length)."""
+        what = "ppo_gradient"
+        K, N, S, P = self._pg_lanes(what, obs, policies)                    # (here too: they size what is allocated)
+        if isinstance(sigma, bool) or sigma is None:
+            raise ValueError(f"{what}: sigma must be a float, a [2] tensor or an [{N}, 2] tensor, got {sigma!r}")
+        if isinstance(sigma, (int, float)):
+            sigma = torch.full((2,), float(sigma), dtype=self.dtype, device=self.device)
+        elif isinstance(sigma, torch.Tensor) and sigma.dim() == 2:
+            sigma = self._kernel_view(what, sigma, (N, 2), "sigma", (1, 0))  # the [2, N] an [N, 2] sigma is a view of goes on as it is
+        D, i32 = self.D, torch.int32
+        if weights is None or weights_old is None:
+            raise ValueError(f"{what}: weights and weights_old are required, each [{P}, 2, {D + 1}]")
+        w = self._kernel_view(what, weights, (P, 2, D + 1), "weights", (1, 2, 0))
+        w_old = self._kernel_view(what, weights_old, (P, 2, D + 1), "weights_old", (1, 2, 0))
+        s_new = self._kernel_view(what, sigma_new, (P, 2), "sigma_new", (1, 0))
+        grad, lane, count = self._new(2, D + 1, P), self._new(2, D + 1, N), self._new(ppo.LANE_COUNTS, N, dtype=i32)
+        stat, lane_stat = self._new(ppo.STATS, P), self._new(ppo.STATS, N)
+        steps, clipped, gated, valid = self._new(P, dtype=i32), self._new(2, P, dtype=i32), self._new(P, dtype=i32), self._new(P, dtype=i32)
+        lsig = self._new(2, P) if want_log_sigma else None
+        lane_lsig = self._new(2, N) if want_log_sigma else None
+        ratio = self._new(K, N) if want_ratio else None
+        self.ppo_gradient_into(obs, noise, sigma, w, w_old, adv, grad, lane, lane_stat, count, policies=P, clip=clip, obs0=obs0,
+                               actions=actions, tanh=tanh, length=length, sigma_new=s_new, lsig_grad=lsig, lane_lsig=lane_lsig, stat=stat,
+                               steps=steps, clipped=clipped, gated=gated, valid=valid, ratio=ratio)
+        return (grad.permute(2, 0, 1), stat.t(), steps, clipped.t(), gated, valid, None if lsig is None else lsig.t(),
+                lane.permute(2, 0, 1) if want_lane else None, ratio)
