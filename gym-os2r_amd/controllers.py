@@ -1,6 +1,6 @@
 """The controller calls of a HipSim: LQR gains, the iLQR backward pass, its line search with and without a steered mu, the MPPI
 update, the cross-entropy update, the particle-filter update, the Kalman filter update, the two calls of the unscented Kalman filter (its sigma points and its update), the
-score-function policy gradient, the two calls of the critic (GAE(lambda) and the linear value fit) and the clipped-surrogate (PPO) gradient, each as an allocation-free ``*_into`` on tensors in the kernel's layout and an allocating
+score-function policy gradient, the two calls of the critic (GAE(lambda) and the linear value fit), the clipped-surrogate (PPO) gradient and the natural-gradient step, each as an allocation-free ``*_into`` on tensors in the kernel's layout and an allocating
 wrapper around it.  ``Controllers`` is the plain base class HipSim (gym_os2r_amd.sim) inherits them from; it uses the handle's
 ``_out``, ``_in``, ``_new``, ``_layout``, ``_stream`` and ``_check``.
 
@@ -15,7 +15,7 @@ import math
 
 import torch
 
-from . import abi, cem, control, critic, ekf, mppi, pf, pg, ppo, search, steer, ukf
+from . import abi, cem, control, critic, ekf, mppi, npg, pf, pg, ppo, search, steer, ukf
 from ._lib import Os2rError, _ptr
 
 NOMINAL_KEYS = ("cost", "actions", "obs", "end_obs", "lx", "lu", "p_final")
@@ -1256,3 +1256,92 @@ class Controllers:
                                steps=steps, clipped=clipped, gated=gated, valid=valid, ratio=ratio)
         return (grad.permute(2, 0, 1), stat.t(), steps, clipped.t(), gated, valid, None if lsig is None else lsig.t(),
                 lane.permute(2, 0, 1) if want_lane else None, ratio)
+
+    # -- the natural-gradient step ------------------------------------------------------------
+    def natural_step_into(self, obs, sigma, grad, step, lane_mom, mom, lane_count, *, policies: int = 1, obs0=None, actions=None,
+                          tanh: bool = False, length=None, lsig_grad=None, damping: float = 1e-3, kl: float = 0.01, dir=None,
+                          lsig_step=None, beta=None, quad=None, failed=None, steps=None, open=None, valid=None):
+        """Allocation-free natural-gradient step on tensors in the kernel's layouts (include/os2r_npg.h: os2rn_natural_step; the
+        arithmetic and its order are spelled out there).  With P = policies, S samples, N = S P lanes (lane s P + p: sample s of
+        policy p), K steps and E = gym_os2r_amd.npg.moments(D): obs [K, N, D], obs0 [N, D] (None: obs[k] is what step k's action
+        saw), actions [K, N, 2] (required unless tanh), sigma [2] or [2, N], length [N] int32 (None: K), grad [2, D+1, P] and
+        lsig_grad [2, P] (or None) are read, damping >= 0 and kl >= 0; step [2, D+1, P], lane_mom [E, N], mom [E, P] and lane_count
+        [4, N] int32 (all four required: each launch reads what the one before it wrote), lsig_step [2, P] (exactly with
+        lsig_grad), dir [2, D+1, P], beta [P], quad [P], failed [3, P] int32, steps [P] int32, open [2, P] int32 and valid [P] int32
+        are written, each of the last seven or None (without steps or open the solve adds those integers up itself, a lane
+        after the other: give both where S is large).  Shapes, dtypes, device, contiguity, alignment and overlap are checked
+        before the library is called (it takes addresses)."""
+        what = "natural_step"
+        K, N, S, P = self._pg_lanes(what, obs, policies)
+        damp = _finite(what, "damping", math.nan if isinstance(damping, bool) else damping, _not_negative, ">= 0", repr(damping))
+        bound = _finite(what, "kl", math.nan if isinstance(kl, bool) else kl, _not_negative, ">= 0", repr(kl))
+        D, i32 = self.D, torch.int32
+        if any(t is None for t in (sigma, grad, step, lane_mom, mom, lane_count)):
+            raise ValueError(f"{what}: obs, sigma, grad, step, lane_mom, mom and lane_count are required")
+        if not tanh and actions is None:
+            raise ValueError(f"{what}: actions are required unless tanh (where the clip bound, a step's component adds no curvature)")
+        if (lsig_grad is None) != (lsig_step is None):
+            raise ValueError(f"{what}: lsig_grad and lsig_step go together (the step of the widths is that of their gradient)")
+        if tanh:
+            actions = None
+        per_lane = isinstance(sigma, torch.Tensor) and sigma.dim() == 2
+        E = npg.moments(D)
+        inputs = ((obs, (K, N, D), None, "obs"), (obs0, (N, D), None, "obs0"), (actions, (K, N, 2), None, "actions"),
+                  (sigma, (2, N) if per_lane else (2,), None, "sigma"), (length, (N,), i32, "length"), (grad, (2, D + 1, P), None, "grad"),
+                  (lsig_grad, (2, P), None, "lsig_grad"))
+        outputs = ((step, (2, D + 1, P), None, "step"), (dir, (2, D + 1, P), None, "dir"), (lsig_step, (2, P), None, "lsig_step"),
+                   (beta, (P,), None, "beta"), (quad, (P,), None, "quad"), (failed, (3, P), i32, "failed"), (steps, (P,), i32, "steps"),
+                   (open, (2, P), i32, "open"), (valid, (P,), i32, "valid"), (lane_mom, (E, N), None, "lane_mom"), (mom, (E, P), None, "mom"),
+                   (lane_count, (npg.LANE_COUNTS, N), i32, "lane_count"))
+        self._outs(what, inputs + outputs)
+        if actions is not None and actions.data_ptr() % (2 * actions.element_size()):
+            raise ValueError(f"{what}: actions must be aligned to a pair of its elements")
+        self._no_overlap(what, inputs, outputs)
+        _call(npg, "os2rn_natural_step", "os2rn_last_error", C.byref(self._layout()), K, P, S,
+              (npg.TANH if tanh else 0) | (npg.SIGMA_PER_LANE if per_lane else 0), _ptr(obs), _ptr(obs0), _ptr(actions), _ptr(sigma),
+              _ptr(length), _ptr(grad), _ptr(lsig_grad), damp, bound, _ptr(step), _ptr(dir), _ptr(lsig_step), _ptr(beta), _ptr(quad),
+              _ptr(failed), _ptr(steps), _ptr(open), _ptr(valid), _ptr(lane_mom), _ptr(mom), _ptr(lane_count), self._stream())
+
+    def natural_step(self, obs, sigma, grad, *, policies: int = 1, obs0=None, actions=None, tanh: bool = False, length=None, lsig_grad=None,
+                     damping: float = 1e-3, kl: float = 0.01, want_dir: bool = False, want_counts: bool = True):
+        """The natural-gradient step of P = policies linear-Gaussian policies in one call (include/os2r_npg.h:
+        os2rn_natural_step): obs, actions, length, obs0, sigma (a float, [2] or [N, 2]) and tanh are those of policy_gradient,
+        all taken without a copy; grad [P, 2, D+1] is what policy_gradient or ppo_gradient returned (a permuted view of the
+        kernel's [2, D+1, P] goes on without a copy), lsig_grad [P, 2] their gradient of log sigma (None: the widths stay).
+        Per action component j the Fisher matrix of the mean weights is the mean over the counted steps of the policy's valid
+        lanes of [x; 1][x; 1]' / sigma_j^2 on the steps where the component was open (sigma_j > 0 and, unless tanh, the clip did
+        not bind); d_j solves (F_j + damping I) d_j = grad_j / steps by a Cholesky factor, the widths have the Fisher entry
+        2 open_j / steps.  With the widths unchanged the mean KL divergence of a step Delta is exactly 1/2 Delta' F Delta, so
+        step = sqrt(2 kl / (g . d)) d has the divergence kl (up to the damping): a step size in nats, the same for every policy.
+        kl = 0: step = d, the plain natural gradient.  A lane one of whose moment sums is not finite is left out.
+        -> (step [P, 2, D+1]: a permuted view of the kernel's layout, weights + step is what rollout_policy takes next;
+        lsig_step [P, 2] | None: the step of log sigma; beta [P]: the factor on d; quad [P]: g . d; failed [P, 3] int32: per
+        component 0 or the column + 1 at which its factor failed (d_j = 0), and 1 where g . d was not finite and positive
+        (step = 0); steps [P] int32 | None: the counted steps; open [P, 2] int32 | None: the open steps of each component; valid
+        [P] int32 | None: the valid lanes -- the three None without want_counts; dir [P, 2, D+1] | None: d itself)."""
+        what = "natural_step"
+        K, N, S, P = self._pg_lanes(what, obs, policies)                    # (here too: they size what is allocated)
+        if isinstance(sigma, bool) or sigma is None:
+            raise ValueError(f"{what}: sigma must be a float, a [2] tensor or an [{N}, 2] tensor, got {sigma!r}")
+        if isinstance(sigma, (int, float)):
+            sigma = torch.full((2,), float(sigma), dtype=self.dtype, device=self.device)
+        elif isinstance(sigma, torch.Tensor) and sigma.dim() == 2:
+            sigma = self._kernel_view(what, sigma, (N, 2), "sigma", (1, 0))  # the [2, N] an [N, 2] sigma is a view of goes on as it is
+        D, i32 = self.D, torch.int32
+        if grad is None:
+            raise ValueError(f"{what}: grad is required, [{P}, 2, {D + 1}]")
+        g = self._kernel_view(what, grad, (P, 2, D + 1), "grad", (1, 2, 0))
+        g_ls = self._kernel_view(what, lsig_grad, (P, 2), "lsig_grad", (1, 0))
+        E = npg.moments(D)
+        step, lane_mom, mom, count = self._new(2, D + 1, P), self._new(E, N), self._new(E, P), self._new(npg.LANE_COUNTS, N, dtype=i32)
+        beta, quad, failed = self._new(P), self._new(P), self._new(3, P, dtype=i32)
+        # the integer totals are always asked of the sum launch: the solve reads them
+        steps, opened, valid = self._new(P, dtype=i32), self._new(2, P, dtype=i32), self._new(P, dtype=i32)
+        direction = self._new(2, D + 1, P) if want_dir else None
+        ls_step = self._new(2, P) if g_ls is not None else None
+        self.natural_step_into(obs, sigma, g, step, lane_mom, mom, count, policies=P, obs0=obs0, actions=actions, tanh=tanh, length=length,
+                               lsig_grad=g_ls, damping=damping, kl=kl, dir=direction, lsig_step=ls_step, beta=beta, quad=quad, failed=failed,
+                               steps=steps, open=opened, valid=valid)
+        return (step.permute(2, 0, 1), None if ls_step is None else ls_step.t(), beta, quad, failed.t(),
+                steps if want_counts else None, opened.t() if want_counts else None, valid if want_counts else None,
+                None if direction is None else direction.permute(2, 0, 1))

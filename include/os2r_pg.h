@@ -12,8 +12,8 @@
  * Plain C: no torch / pybind / HIP types appear in any signature.
  *
  * Out of scope: MLP policies, value-function bootstrapping and GAE(lambda), the optimiser step, importance ratios and PPO
- * clipping, natural-gradient and Fisher terms, a weight per policy on the baseline, scheduled policies (the tables of
- * os2r_rollout_policy_scheduled, whose gradient would carry a slot index).
+ * clipping, natural-gradient and Fisher terms (since built as `libos2r_npg.so`), a weight per policy on the baseline, scheduled
+ * policies (the tables of os2r_rollout_policy_scheduled, whose gradient would carry a slot index).
  */
 #ifndef OS2R_PG_H_
 #define OS2R_PG_H_

@@ -16,7 +16,7 @@
  * Out of scope: MLP policies, scheduled policies, the optimiser step and the entropy bonus (one torch line each), advantage
  * normalisation inside the call, a value-loss clip, minibatching within a policy's lanes, the density of a component on which
  * the action clip bound (it is left out of the ratio just as the score-function gradient leaves it out of the score),
- * natural-gradient and Fisher terms, a fused advantage + gradient launch.
+ * natural-gradient and Fisher terms (since built as `libos2r_npg.so`), a fused advantage + gradient launch.
  */
 #ifndef OS2R_PPO_H_
 #define OS2R_PPO_H_
