@@ -1,6 +1,6 @@
 """The controller calls of a HipSim: LQR gains, the iLQR backward pass, its line search with and without a steered mu, the MPPI
 update, the cross-entropy update, the particle-filter update, the Kalman filter update, the two calls of the unscented Kalman filter (its sigma points and its update), the
-score-function policy gradient, the two calls of the critic (GAE(lambda) and the linear value fit), the clipped-surrogate (PPO) gradient and the natural-gradient step, each as an allocation-free ``*_into`` on tensors in the kernel's layout and an allocating
+score-function policy gradient, the two calls of the critic (GAE(lambda) and the linear value fit), the clipped-surrogate (PPO) gradient, the natural-gradient step and the two calls of evolution-strategy search (the perturbation and the ARS update), each as an allocation-free ``*_into`` on tensors in the kernel's layout and an allocating
 wrapper around it.  ``Controllers`` is the plain base class HipSim (gym_os2r_amd.sim) inherits them from; it uses the handle's
 ``_out``, ``_in``, ``_new``, ``_layout``, ``_stream`` and ``_check``.
 
@@ -15,7 +15,7 @@ import math
 
 import torch
 
-from . import abi, cem, control, critic, ekf, mppi, npg, pf, pg, ppo, search, steer, ukf
+from . import abi, cem, control, critic, ekf, es, mppi, npg, pf, pg, ppo, search, steer, ukf
 from ._lib import Os2rError, _ptr
 
 NOMINAL_KEYS = ("cost", "actions", "obs", "end_obs", "lx", "lu", "p_final")
@@ -1345,3 +1345,126 @@ class Controllers:
         return (step.permute(2, 0, 1), None if ls_step is None else ls_step.t(), beta, quad, failed.t(),
                 steps if want_counts else None, opened.t() if want_counts else None, valid if want_counts else None,
                 None if direction is None else direction.permute(2, 0, 1))
+
+    # -- evolution strategies: antithetic perturbations and the ARS V1-t update -------------
+    def _es_shape(self, what, theta, directions, generation, seed, pop_offset):
+        """theta [M, 2, D+1] and the integers both calls share -> (M, S, N = 2 S M, seed, pop_offset, generation)."""
+        S = _count(what, "directions", directions)
+        if S > es.MAX_DIRECTIONS:
+            raise ValueError(f"{what}: directions must be below 2^27, got {S}")
+        if not isinstance(theta, torch.Tensor) or theta.dim() != 3 or theta.shape[0] < 1:
+            raise ValueError(f"{what}: theta must be a tensor [M, 2, {self.D + 1}] with M >= 1, got {tuple(getattr(theta, 'shape', ()))}")
+        M = int(theta.shape[0])
+        if 2 * S * M > 2 ** 31 - 1:
+            raise ValueError(f"{what}: 2 x directions x populations = {2 * S * M} exceeds 2^31 - 1")
+        words = []
+        for name, v in (("generation", generation), ("pop_offset", pop_offset)):
+            if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v < 2 ** 32:
+                raise ValueError(f"{what}: {name} must be an integer in 0..2^32 - 1, got {v!r}")
+            words.append(v)
+        if seed is not None and (isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 64):
+            raise ValueError(f"{what}: seed must be None (the handle's) or an integer in 0..2^64 - 1, got {seed!r}")
+        return M, S, 2 * S * M, seed, words[1], words[0]
+
+    def _es_aligned(self, what, rows):
+        for t, name in rows:
+            if t is not None and t.data_ptr() % (2 * t.element_size()):
+                raise ValueError(f"{what}: {name} must be aligned to a pair of its elements")
+
+    def es_perturb_into(self, theta, weights, *, directions: int, nu: float, generation: int, seed=None, pop_offset: int = 0, delta=None):
+        """Allocation-free antithetic perturbation of M policies along S = directions directions each, in one launch
+        (include/os2r_es.h: os2ra_es_perturb; the arithmetic is spelled out there).  theta [M, 2, D+1] is read; weights [N, 2, D+1]
+        with N = 2 S M lanes and delta [S M, 2, D+1] (or None) are written: lane (h S + s) M + m is theta_m + nu delta[m, s] for
+        h = 0 and theta_m - nu delta[m, s] for h = 1, what rollout_policy takes as per-environment weights; row s M + m of delta
+        is delta[m, s].  The directions are a pure function of (seed, pop_offset + m, s, generation) under the stepper's counter
+        RNG (stream 6), drawn in double and rounded once to the handle's dtype; seed None is the handle's seed, generation and
+        pop_offset are 32-bit words.  nu >= 0.  Shapes, dtypes, device, contiguity, alignment and overlap are checked before the
+        library is called (it takes addresses)."""
+        what = "es_perturb"
+        M, S, N, seed, off, gen = self._es_shape(what, theta, directions, generation, seed, pop_offset)
+        scale = _finite(what, "nu", math.nan if isinstance(nu, bool) else nu, _not_negative, ">= 0", repr(nu))
+        if weights is None:
+            raise ValueError(f"{what}: theta and weights are required")
+        D = self.D
+        inputs = ((theta, (M, 2, D + 1), None, "theta"),)
+        outputs = ((weights, (N, 2, D + 1), None, "weights"), (delta, (S * M, 2, D + 1), None, "delta"))
+        self._outs(what, inputs + outputs)
+        self._es_aligned(what, ((theta, "theta"), (weights, "weights"), (delta, "delta")))
+        self._no_overlap(what, inputs, outputs)
+        _call(es, "os2ra_es_perturb", "os2ra_last_error", C.byref(self._layout()), M, S, 0, int(self.cfg.seed) if seed is None else seed, off,
+              gen, _ptr(theta), scale, _ptr(weights), _ptr(delta), self._stream())
+
+    def es_perturb(self, theta, directions: int, nu: float, generation: int, seed=None, pop_offset: int = 0, want_delta: bool = False):
+        """The 2 S M perturbed policies of one generation of evolution-strategy search, in one launch (include/os2r_es.h:
+        os2ra_es_perturb): theta [M, 2, D+1] holds M policies (populations) as rollout_policy takes one, S = directions.
+        -> (weights [N, 2, D+1], N = 2 S M: lane (h S + s) M + m is theta_m + nu delta[m, s] (h = 0) or theta_m - nu delta[m, s]
+        (h = 1) -- rollout_policy(K, weights, first_episode=True) on a handle of N environments returns what es_update takes,
+        and copy_envs_from(real, arange(N) % M) lines the environments up without a gather; delta [S M, 2, D+1] | None: the
+        directions, row s M + m, for tests and for callers who want them -- es_update does not read them, it regenerates them
+        from (seed, pop_offset + m, s, generation)).  Populations that differ in pop_offset only draw different directions; a
+        shard of populations with pop_offset = a draws what populations a, a + 1, ... of one call would."""
+        what = "es_perturb"
+        M, S, N, _, _, _ = self._es_shape(what, theta, directions, generation, seed, pop_offset)   # (here too: they size what is allocated)
+        weights = self._new(N, 2, self.D + 1)
+        delta = self._new(S * M, 2, self.D + 1) if want_delta else None
+        self.es_perturb_into(theta, weights, directions=S, nu=nu, generation=generation, seed=seed, pop_offset=pop_offset, delta=delta)
+        return weights, delta
+
+    def es_update_into(self, returns, theta, theta_new, sigma_r, count, used, kept, *, directions: int, generation: int, step_size: float,
+                       top: int = 0, sigma_floor: float = 1e-8, seed=None, pop_offset: int = 0, grad=None, score=None):
+        """Allocation-free ARS V1-t update of M policies from the returns of their 2 S lanes (include/os2r_es.h: os2ra_es_update;
+        the arithmetic and its order are spelled out there).  returns [N] (N = 2 S M, the lanes of es_perturb) and theta
+        [M, 2, D+1] are read; theta_new [M, 2, D+1], sigma_r [M], count [M] int32, used [M] int32 and kept [S M] int32 (all
+        required: kept is the scratch the sums read where top selects) and grad [M, 2, D+1] (or None) are written; score [S M]
+        in the handle's dtype is scratch, required where 0 < top < directions and not touched otherwise.  step_size and
+        sigma_floor >= 0, top >= 0.  generation, seed and pop_offset are those of the es_perturb call whose weights were rolled
+        out.  An output may not overlap an input: the caller swaps theta and theta_new.  Shapes, dtypes, device, contiguity,
+        alignment and overlap are checked before the library is called (it takes addresses)."""
+        what = "es_update"
+        M, S, N, seed, off, gen = self._es_shape(what, theta, directions, generation, seed, pop_offset)
+        if isinstance(top, bool) or not isinstance(top, int) or top < 0:
+            raise ValueError(f"{what}: top must be an integer >= 0 (0: every direction), got {top!r}")
+        step = _finite(what, "step_size", math.nan if isinstance(step_size, bool) else step_size, _not_negative, ">= 0", repr(step_size))
+        floor = _finite(what, "sigma_floor", math.nan if isinstance(sigma_floor, bool) else sigma_floor, _not_negative, ">= 0",
+                        repr(sigma_floor))
+        if any(t is None for t in (returns, theta_new, sigma_r, count, used, kept)):
+            raise ValueError(f"{what}: returns, theta, theta_new, sigma_r, count, used and kept are required")
+        select = 0 < top < S
+        if select and score is None:
+            raise ValueError(f"{what}: score [{S * M}] is required where 0 < top < directions (the rank launch reads it)")
+        D, i32 = self.D, torch.int32
+        inputs = ((returns, (N,), None, "returns"), (theta, (M, 2, D + 1), None, "theta"))
+        outputs = ((theta_new, (M, 2, D + 1), None, "theta_new"), (sigma_r, (M,), None, "sigma_r"), (count, (M,), i32, "count"),
+                   (used, (M,), i32, "used"), (grad, (M, 2, D + 1), None, "grad"), (kept, (S * M,), i32, "kept"),
+                   (score if select else None, (S * M,), None, "score"))
+        self._outs(what, inputs + outputs)
+        self._es_aligned(what, ((theta, "theta"), (theta_new, "theta_new"), (grad, "grad")))
+        self._no_overlap(what, inputs, outputs)
+        _call(es, "os2ra_es_update", "os2ra_last_error", C.byref(self._layout()), M, S, min(top, 2 ** 31 - 1), 0,
+              int(self.cfg.seed) if seed is None else seed, off, gen, _ptr(returns), _ptr(theta), step, floor, _ptr(theta_new), _ptr(sigma_r),
+              _ptr(count), _ptr(used), _ptr(grad), _ptr(kept), _ptr(score) if select else None, self._stream())
+
+    def es_update(self, returns, theta, directions: int, generation: int, step_size: float, top: int = 0, sigma_floor: float = 1e-8,
+                  seed=None, pop_offset: int = 0, want_grad: bool = False, want_kept: bool = False):
+        """The update of augmented random search (ARS V1-t, Mania et al. 2018) of M policies in one call (include/os2r_es.h:
+        os2ra_es_update): returns [N] is what rollout_policy(K, weights, first_episode=True) returned for the weights of
+        es_perturb(theta, directions, nu, generation, ...), as it lies on the device; generation, seed and pop_offset are that
+        call's.  Per population: a direction is valid where both of its returns are finite; the b' = min(top or S, valid) valid
+        directions of the largest max(r+, r-) are kept (equal scores: the lower s first); sigma_R is the standard deviation
+        (ddof 0) of the 2 b' kept returns, at least sigma_floor; theta_new = theta + step_size / (b' sigma_R) sum (r+ - r-) delta
+        over the kept directions, the directions regenerated from the counter RNG, not read.  A population without a valid
+        direction keeps theta and reports sigma_R = 0.
+        -> (theta_new [M, 2, D+1]; sigma_r [M]; count [M] int32: the valid directions; used [M] int32: b'; grad [M, 2, D+1] |
+        None: the step without step_size, for the caller's own optimiser; kept [S M] int32 | None: 1 where direction s of
+        population m, at s M + m, was kept)."""
+        what = "es_update"
+        M, S, N, _, _, _ = self._es_shape(what, theta, directions, generation, seed, pop_offset)   # (here too: they size what is allocated)
+        D, i32 = self.D, torch.int32
+        theta_new, sigma_r = self._new(M, 2, D + 1), self._new(M)
+        count, used, kept = self._new(M, dtype=i32), self._new(M, dtype=i32), self._new(S * M, dtype=i32)
+        grad = self._new(M, 2, D + 1) if want_grad else None
+        select = isinstance(top, int) and 0 < top < S
+        score = self._new(S * M) if select else None
+        self.es_update_into(returns, theta, theta_new, sigma_r, count, used, kept, directions=S, generation=generation, step_size=step_size,
+                            top=top, sigma_floor=sigma_floor, seed=seed, pop_offset=pop_offset, grad=grad, score=score)
+        return theta_new, sigma_r, count, used, grad, kept if want_kept else None
