@@ -431,6 +431,36 @@ __device__ __forceinline__ float rcp_t(float x) {
   float r = __builtin_amdgcn_rcpf(x);              // 1 ulp estimate; one Newton step
   return __builtin_fmaf(__builtin_fmaf(-x, r, 1.0f), r, r);
 }
+// rcp_t of N independent values side by side: the estimates first, then the Newton steps step by step -- per value the
+// operations of rcp_t, bit for bit.  One chain after the other every instruction waits for the one before it, which a wave
+// that owns its SIMD sits out (round 8); the barriers are no instructions and keep the steps from being serialised again.
+template <int N>
+__device__ __forceinline__ void rcp_group(const double (&x)[N], double (&r)[N]) {
+  double e[N];
+#pragma unroll
+  for (int i = 0; i < N; ++i) r[i] = __builtin_amdgcn_rcp(x[i]);
+#pragma unroll
+  for (int s = 0; s < 2; ++s) {
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int i = 0; i < N; ++i) e[i] = __builtin_fma(-x[i], r[i], 1.0);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int i = 0; i < N; ++i) r[i] = __builtin_fma(e[i], r[i], r[i]);
+  }
+}
+template <int N>
+__device__ __forceinline__ void rcp_group(const float (&x)[N], float (&r)[N]) {
+  float e[N];
+#pragma unroll
+  for (int i = 0; i < N; ++i) r[i] = __builtin_amdgcn_rcpf(x[i]);
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int i = 0; i < N; ++i) e[i] = __builtin_fmaf(-x[i], r[i], 1.0f);
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int i = 0; i < N; ++i) r[i] = __builtin_fmaf(e[i], r[i], r[i]);
+}
 __device__ __forceinline__ double rsqrt_t(double x) {
   double r = __builtin_amdgcn_rsq(x);
   // r <- r * (1.5 - 0.5 x r^2), twice
@@ -646,6 +676,14 @@ __device__ __forceinline__ void substep(const MD& md, const Params<T, MD, DR>& p
                                         ) {
   constexpr int NQ = MD::NQ;
   constexpr unsigned CMASK = CONTACT ? MD::CMASK : 0u;
+  // Round 8 (docs/studies/round8_chain_interleave.md): chains that are independent of each other advance side by side instead
+  // of one after the other -- a wave that owns its SIMD issues a dependent fp64 instruction every 6.1 cycles, an independent
+  // one every 3.6 -- and the row set-up of the compiled-in robots takes the factor from registers.  Operations, operands and
+  // the order in which every sum takes its terms are the parent's.  The fp64 sweeps-only kernels of the compiled-in robots
+  // keep the parent's form: two of their 5-dof os2r_linearize kernels (and, before, one step kernel) sit where the register
+  // allocator starts to spill, and the sin/cos form or the factor in registers tips them over (2-4 VGPR spills each).
+  // The fp32 kernels keep it too: they run two waves per SIMD, which fill each other's gaps, and were 0.5 % slower with it.
+  constexpr bool kSideBySide = sizeof(T) == 8 && !(SOLVER == kSolverSweeps && MD::kStatic);
   const T inv_dt = rcp_t(dt);
   // the first parameter pair of the inward pass is requested before anything else
   const T m_first = par.mass(NQ - 1), damp_first = par.damping(NQ - 1);
@@ -666,22 +704,60 @@ __device__ __forceinline__ void substep(const MD& md, const Params<T, MD, DR>& p
     // side only): what a lane computes must not depend on who shares its wave.
     if constexpr (COUNT) wc.full_sincos += __ballot(!small) != 0ull ? 1u : 0u;
     if (small) {
+      if constexpr (kSideBySide) {
+        // The 2 NQ polynomials (sin and cos of every joint) advance together, term by term, then the NQ turns; written joint
+        // by joint (below) 18 of a joint's 21 instructions wait for the one before them.  Operations and operands are those
+        // of the form below; the barriers (no instructions) keep the compiler from putting the terms back in a row.
+        T d[NQ], z[NQ], dz[NQ], p[NQ], r[NQ];
 #pragma unroll
-      for (int i = 0; i < NQ; ++i) {
-        const T d = dt * qd[i], z = d * d;
-        T p = fma_t(z, T(-1.0 / 39916800.0), T(1.0 / 362880.0));
-        p = fma_t(z, p, T(-1.0 / 5040.0));
-        p = fma_t(z, p, T(1.0 / 120.0));
-        p = fma_t(z, p, T(-1.0 / 6.0));
-        const T sd = fma_t(d * z, p, d);
-        T r = fma_t(z, T(-1.0 / 3628800.0), T(1.0 / 40320.0));
-        r = fma_t(z, r, T(-1.0 / 720.0));
-        r = fma_t(z, r, T(1.0 / 24.0));
-        r = fma_t(z, r, T(-0.5));
-        const T cm = z * r;
-        const T s0 = sn[i], c0 = cs[i];
-        sn[i] = s0 + fma_t(c0, sd, s0 * cm);
-        cs[i] = c0 + fma_t(-s0, sd, c0 * cm);
+        for (int i = 0; i < NQ; ++i) { d[i] = dt * qd[i]; z[i] = d[i] * d[i]; }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int i = 0; i < NQ; ++i) {
+          p[i] = fma_t(z[i], T(-1.0 / 39916800.0), T(1.0 / 362880.0));
+          r[i] = fma_t(z[i], T(-1.0 / 3628800.0), T(1.0 / 40320.0));
+          dz[i] = d[i] * z[i];
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int i = 0; i < NQ; ++i) { p[i] = fma_t(z[i], p[i], T(-1.0 / 5040.0)); r[i] = fma_t(z[i], r[i], T(-1.0 / 720.0)); }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int i = 0; i < NQ; ++i) { p[i] = fma_t(z[i], p[i], T(1.0 / 120.0)); r[i] = fma_t(z[i], r[i], T(1.0 / 24.0)); }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int i = 0; i < NQ; ++i) { p[i] = fma_t(z[i], p[i], T(-1.0 / 6.0)); r[i] = fma_t(z[i], r[i], T(-0.5)); }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int i = 0; i < NQ; ++i) { p[i] = fma_t(dz[i], p[i], d[i]); r[i] = z[i] * r[i]; }   // p: sin d, r: cos d - 1
+        __builtin_amdgcn_sched_barrier(0);
+        T ts[NQ], tc[NQ];
+#pragma unroll
+        for (int i = 0; i < NQ; ++i) { ts[i] = sn[i] * r[i]; tc[i] = cs[i] * r[i]; }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int i = 0; i < NQ; ++i) { ts[i] = fma_t(cs[i], p[i], ts[i]); tc[i] = fma_t(-sn[i], p[i], tc[i]); }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int i = 0; i < NQ; ++i) { sn[i] = sn[i] + ts[i]; cs[i] = cs[i] + tc[i]; }
+      } else {
+#pragma unroll
+        for (int i = 0; i < NQ; ++i) {
+          const T d = dt * qd[i], z = d * d;
+          T p = fma_t(z, T(-1.0 / 39916800.0), T(1.0 / 362880.0));
+          p = fma_t(z, p, T(-1.0 / 5040.0));
+          p = fma_t(z, p, T(1.0 / 120.0));
+          p = fma_t(z, p, T(-1.0 / 6.0));
+          const T sd = fma_t(d * z, p, d);
+          T r = fma_t(z, T(-1.0 / 3628800.0), T(1.0 / 40320.0));
+          r = fma_t(z, r, T(-1.0 / 720.0));
+          r = fma_t(z, r, T(1.0 / 24.0));
+          r = fma_t(z, r, T(-0.5));
+          const T cm = z * r;
+          const T s0 = sn[i], c0 = cs[i];
+          sn[i] = s0 + fma_t(c0, sd, s0 * cm);
+          cs[i] = c0 + fma_t(-s0, sd, c0 * cm);
+        }
       }
     } else if (ok) {
       // one range check for all joints of the lane, so the five evaluations are straight-line code
@@ -918,6 +994,11 @@ __device__ __forceinline__ void substep(const MD& md, const Params<T, MD, DR>& p
   constexpr int kLc = 0;                       // Lc[i][k], k <= i, at kLc + i*(i+1)/2 + k (LDS mirror, after the pass)
   auto Lcs = [&](int i, int k) -> T& { return L(kLc + i * (i + 1) / 2 + k); };
   T Lc[NQ][NQ];   // lower triangle, also mirrored to LDS for the contact-row setup
+  // ... except in the kernels of the compiled-in robots (round 8, as kKeep): Lc is live up to the sweeps there, the row set-up
+  // takes its copy from the registers and the mirror's 15 stores and up to 31 loads per iteration go; slots and lds_words stay.
+  // As for kKeep, an empty asm stands where every store and every load was: without those at the loads the results differ
+  // from the parent's in the last bits (round 7 study, 3).
+  constexpr bool kLcKeep = MD::kStatic && kSideBySide;
   T Ldi[NQ];      // 1 / Lc[i][i] = sqrt(D_i)
   {
     T uk[NQ][NQ];            // uk[k][i]: joint-space force of column k at joint i (i <= k)
@@ -1005,8 +1086,14 @@ __device__ __forceinline__ void substep(const MD& md, const Params<T, MD, DR>& p
   for (int j = 0; j < NQ; ++j) {
     T mjj = 0;
 #pragma unroll
-    for (int k = 0; k <= j; ++k) { mjj += Lc[j][k] * Lc[j][k]; Lcs(j, k) = Lc[j][k]; }
-    idj[j] = mjj > T(0) ? rcp_t(mjj) : T(0);
+    for (int k = 0; k <= j; ++k) {
+      mjj += Lc[j][k] * Lc[j][k];
+      // (the kernels that keep the factor's rows in registers for the row set-up: a pin where the mirror's store was, as for kKeep)
+      if constexpr (kLcKeep) pin_use(Lc[j][k]);
+      else Lcs(j, k) = Lc[j][k];
+    }
+    if constexpr (kSideBySide) idj[j] = mjj;     // its reciprocal is taken with the other joints', where step 6 needs it
+    else idj[j] = mjj > T(0) ? rcp_t(mjj) : T(0);
   }
 #pragma unroll
   for (int i = 0; i < NQ; ++i) {
@@ -1128,18 +1215,53 @@ __device__ __forceinline__ void substep(const MD& md, const Params<T, MD, DR>& p
           T S[3] = {T(0), T(0), T(0)};
           T Wg = T(0), pg = T(0), base = mo;
           auto weigh = [&](const T (&d)[3 * CH], int kk) {
+            if constexpr (kSideBySide) {
+              // the heights of the chunk's four candidates first, level by level -- they are independent of each other, and one
+              // candidate after the other each fma / fma / max / add waits for the one before it --, then the sums in candidate
+              // order: every accumulator takes the terms it took, in the order it took them
+              T in_[CH], mz[CH], wgt[CH];
+              T base_ = base;
 #pragma unroll
-            for (int c = 0; c < CH; ++c) {
-              if (kk + c < k1) {
-                if (MD::cand_starts_run(b, kk + c, ga)) {
-                  W += Wg; S[ga] = fma_t(pg, Wg, S[ga]);
-                  Wg = T(0); pg = d[3 * c + ga];
-                  base = fma_t(-Rw[6 + ga], pg, mo);
+              for (int c = 0; c < CH; ++c) {
+                if (kk + c < k1) {
+                  if (MD::cand_starts_run(b, kk + c, ga)) base_ = fma_t(-Rw[6 + ga], d[3 * c + ga], mo);
+                  in_[c] = fma_t(-Rw[6 + a2], d[3 * c + a2], base_);
                 }
-                const T p1 = d[3 * c + a1], p2 = d[3 * c + a2];
-                const T mz = fma_t(-Rw[6 + a1], p1, fma_t(-Rw[6 + a2], p2, base));
-                const T wgt = fmax_t(mz, T(0));
-                Wg += wgt; S[a1] = fma_t(wgt, p1, S[a1]); S[a2] = fma_t(wgt, p2, S[a2]);
+              }
+              base = base_;
+              __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+              for (int c = 0; c < CH; ++c)
+                if (kk + c < k1) mz[c] = fma_t(-Rw[6 + a1], d[3 * c + a1], in_[c]);
+              __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+              for (int c = 0; c < CH; ++c)
+                if (kk + c < k1) wgt[c] = fmax_t(mz[c], T(0));
+              __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+              for (int c = 0; c < CH; ++c) {
+                if (kk + c < k1) {
+                  if (MD::cand_starts_run(b, kk + c, ga)) {
+                    W += Wg; S[ga] = fma_t(pg, Wg, S[ga]);
+                    Wg = T(0); pg = d[3 * c + ga];
+                  }
+                  Wg += wgt[c]; S[a1] = fma_t(wgt[c], d[3 * c + a1], S[a1]); S[a2] = fma_t(wgt[c], d[3 * c + a2], S[a2]);
+                }
+              }
+            } else {
+#pragma unroll
+              for (int c = 0; c < CH; ++c) {
+                if (kk + c < k1) {
+                  if (MD::cand_starts_run(b, kk + c, ga)) {
+                    W += Wg; S[ga] = fma_t(pg, Wg, S[ga]);
+                    Wg = T(0); pg = d[3 * c + ga];
+                    base = fma_t(-Rw[6 + ga], pg, mo);
+                  }
+                  const T p1 = d[3 * c + a1], p2 = d[3 * c + a2];
+                  const T mz = fma_t(-Rw[6 + a1], p1, fma_t(-Rw[6 + a2], p2, base));
+                  const T wgt = fmax_t(mz, T(0));
+                  Wg += wgt; S[a1] = fma_t(wgt, p1, S[a1]); S[a2] = fma_t(wgt, p2, S[a2]);
+                }
               }
             }
           };
@@ -1191,7 +1313,7 @@ __device__ __forceinline__ void substep(const MD& md, const Params<T, MD, DR>& p
         for (int j = 0; j < NQ; ++j)
 #pragma unroll
           for (int k = 0; k < NQ; ++k)
-            if (j <= b && k <= j) lcb[j][k] = Lcs(j, k);
+            if (j <= b && k <= j) lcb[j][k] = kLcKeep ? opaque(Lc[j][k]) : Lcs(j, k);
         __builtin_amdgcn_sched_barrier(kPinDs);
         const T iw = act[b] ? rcp_t(W) : T(0);
         const V3<T> pc = mk(sx * iw, sy * iw, sz * iw);
@@ -1223,9 +1345,18 @@ __device__ __forceinline__ void substep(const MD& md, const Params<T, MD, DR>& p
           }
         }
         // reciprocals once per iteration of the physics, not once per row update
-        dn[b] = (act[b] && sdn > T(0)) ? rcp_t(sdn) : T(0);
-        dx[b] = (act[b] && sdx > T(0)) ? rcp_t(sdx) : T(0);
-        dy[b] = (act[b] && sdy > T(0)) ? rcp_t(sdy) : T(0);
+        if constexpr (kSideBySide) {
+          const T sd[3] = {sdn, sdx, sdy};
+          T rd[3];
+          rcp_group(sd, rd);     // the three chains side by side
+          dn[b] = (act[b] && sdn > T(0)) ? rd[0] : T(0);
+          dx[b] = (act[b] && sdx > T(0)) ? rd[1] : T(0);
+          dy[b] = (act[b] && sdy > T(0)) ? rd[2] : T(0);
+        } else {
+          dn[b] = (act[b] && sdn > T(0)) ? rcp_t(sdn) : T(0);
+          dx[b] = (act[b] && sdx > T(0)) ? rcp_t(sdx) : T(0);
+          dy[b] = (act[b] && sdy > T(0)) ? rcp_t(sdy) : T(0);
+        }
       }
     }
   }
@@ -1237,6 +1368,14 @@ __device__ __forceinline__ void substep(const MD& md, const Params<T, MD, DR>& p
   for (int b = 0; b < NB; ++b) { ln[b] = 0; lx[b] = 0; ly[b] = 0; }
 #pragma unroll
   for (int j = 0; j < NQ; ++j) lf[j] = 0;
+  if constexpr (kSideBySide) {
+    T mj[NQ];
+#pragma unroll
+    for (int j = 0; j < NQ; ++j) mj[j] = idj[j];
+    rcp_group(mj, idj);     // the NQ chains side by side
+#pragma unroll
+    for (int j = 0; j < NQ; ++j) idj[j] = mj[j] > T(0) ? idj[j] : T(0);
+  }
 #pragma unroll
   for (int j = 0; j < NQ; ++j) {
     fb[j] = opaque(fb[j] * dt);
