@@ -2,7 +2,7 @@
 """Basic augmented random search (ARS, Mania et al. 2018) of a linear policy for Monopod-balance-v1, entirely on the GPU.
 
   python examples/ars_balancing.py [--envs 8192] [--iters 20] [--horizon 500] [--step-size 0.02] [--noise 0.03]
-                                   [--update torch|device] [--populations 1] [--top 0]
+                                   [--update torch|device] [--populations 1] [--top 0] [--normalize]
 
 Every iteration perturbs the policy theta [2, D+1] (row j: weights of action j on the D observations, then its bias) along
 P = envs / 2 random directions delta_p, runs theta + nu*delta_p on environment p and theta - nu*delta_p on environment P + p --
@@ -14,6 +14,11 @@ reshuffled in between: the directions are drawn from the stepper's counter RNG b
 not read, by the launch that updates.  --populations M searches M policies at once on envs / (2 M) directions each -- they
 start alike and differ in the population word of their directions only --, --top b keeps the b best directions of each
 (ARS V1-t); the best and the median population are printed.
+
+--update device --normalize is ARS V2-t: the policy acts on whitened observations, (x - mean) / std with the running mean and
+deviation of everything its population has seen so far (libos2r_norm.so, include/os2r_norm.h).  The policy is linear, so the
+rollout is the same launch: reset -> es_perturb -> norm_fold (theta +- nu delta on whitened observations to weights on raw
+ones, every lane at once) -> rollout_policy -> es_update -> obs_stats (the batch merged into the running statistics).
 """
 import argparse
 import os
@@ -38,11 +43,12 @@ def main():
     ap.add_argument("--update", default="torch", choices=["torch", "device"], help="device: es_perturb / es_update of libos2r_es.so")
     ap.add_argument("--populations", type=int, default=1, help="policies searched at once (--update device)")
     ap.add_argument("--top", type=int, default=0, help="directions kept per population, 0: all (--update device)")
+    ap.add_argument("--normalize", action="store_true", help="ARS V2: running observation whitening (--update device)")
     args = ap.parse_args()
     if args.update == "device":
         return device(args)
-    if args.populations != 1 or args.top != 0:
-        raise SystemExit("--populations and --top need --update device")
+    if args.populations != 1 or args.top != 0 or args.normalize:
+        raise SystemExit("--populations, --top and --normalize need --update device")
     P = args.envs // 2
     if P < 1:
         raise SystemExit("--envs must be at least 2")
@@ -87,16 +93,28 @@ def device(args):
     sigma_r = torch.empty(M, dtype=dt, device=dev)
     count, used, kept = (torch.empty(n, dtype=i32, device=dev) for n in (M, M, S * M))
     score = torch.empty(S * M, dtype=dt, device=dev) if 0 < args.top < S else None
-    print(f"ARS on Monopod-balance-v1: {M} populations x {S} directions x 2 = {N} environments, top {args.top or S}, horizon {args.horizon}, "
+    if args.normalize:                                                             # two running states, swapped every iteration
+        state, state_new = ((torch.zeros(M, dtype=torch.int64, device=dev), torch.zeros(M, D, dtype=dt, device=dev),
+                             torch.zeros(M, D, dtype=dt, device=dev)) for _ in range(2))
+        folded = torch.empty_like(weights)
+        lane_sum, lane_count = torch.empty(2 * D, N, dtype=dt, device=dev), torch.empty(2, N, dtype=i32, device=dev)
+    print(f"ARS{' V2' if args.normalize else ''} on Monopod-balance-v1: {M} populations x {S} directions x 2 = {N} environments, top {args.top or S}, horizon {args.horizon}, "
           f"obs dim {D}", flush=True)
     t0 = time.time()
     for it in range(args.iters):
-        sim.reset()
+        obs0 = sim.reset()
         sim.es_perturb_into(theta, weights, directions=S, nu=args.noise, generation=it)
-        ret, length, _ = sim.rollout_policy(args.horizon, weights, first_episode=True)
+        if args.normalize:
+            sim.norm_fold_into(weights, state, folded, lanes=N)
+            ret, length, outs = sim.rollout_policy(args.horizon, folded, first_episode=True, want_outputs=True)
+        else:
+            ret, length, _ = sim.rollout_policy(args.horizon, weights, first_episode=True)
         sim.es_update_into(ret, theta, theta_new, sigma_r, count, used, kept, directions=S, generation=it, step_size=args.step_size,
                            top=args.top, score=score)
         theta, theta_new = theta_new, theta
+        if args.normalize:
+            sim.obs_stats_into(outs[0], *state_new, lane_sum, lane_count, policies=M, obs0=obs0, length=length, state=state)
+            state, state_new = state_new, state
         per_pop = ret.view(2 * S, M).mean(0)                                       # (for the line below only)
         print(f"iteration {it}: mean return best population {float(per_pop.max()):8.2f}  median {float(per_pop.median()):8.2f}  "
               f"best lane {float(ret.max()):6.1f}  mean episode length {float(length.to(torch.float64).mean()):6.1f}  "

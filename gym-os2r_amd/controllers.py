@@ -1,6 +1,6 @@
 """The controller calls of a HipSim: LQR gains, the iLQR backward pass, its line search with and without a steered mu, the MPPI
 update, the cross-entropy update, the particle-filter update, the Kalman filter update, the two calls of the unscented Kalman filter (its sigma points and its update), the
-score-function policy gradient, the two calls of the critic (GAE(lambda) and the linear value fit), the clipped-surrogate (PPO) gradient, the natural-gradient step and the two calls of evolution-strategy search (the perturbation and the ARS update), each as an allocation-free ``*_into`` on tensors in the kernel's layout and an allocating
+score-function policy gradient, the two calls of the critic (GAE(lambda) and the linear value fit), the clipped-surrogate (PPO) gradient, the natural-gradient step, the two calls of evolution-strategy search (the perturbation and the ARS update) and the three of running observation whitening (the statistics, the fold and the gradient back), each as an allocation-free ``*_into`` on tensors in the kernel's layout and an allocating
 wrapper around it.  ``Controllers`` is the plain base class HipSim (gym_os2r_amd.sim) inherits them from; it uses the handle's
 ``_out``, ``_in``, ``_new``, ``_layout``, ``_stream`` and ``_check``.
 
@@ -15,7 +15,7 @@ import math
 
 import torch
 
-from . import abi, cem, control, critic, ekf, es, mppi, npg, pf, pg, ppo, search, steer, ukf
+from . import abi, cem, control, critic, ekf, es, mppi, norm, npg, pf, pg, ppo, search, steer, ukf
 from ._lib import Os2rError, _ptr
 
 NOMINAL_KEYS = ("cost", "actions", "obs", "end_obs", "lx", "lu", "p_final")
@@ -1468,3 +1468,167 @@ class Controllers:
         self.es_update_into(returns, theta, theta_new, sigma_r, count, used, kept, directions=S, generation=generation, step_size=step_size,
                             top=top, sigma_floor=sigma_floor, seed=seed, pop_offset=pop_offset, grad=grad, score=score)
         return theta_new, sigma_r, count, used, grad, kept if want_kept else None
+
+    # -- running observation whitening: the statistics, the fold and the gradient back ---------
+    def _norm_state(self, what, state, P=None, required=True):
+        """state = (count [P] int64, mean [P, D], m2 [P, D]) of a whitening call -> (count, mean, m2, P), checked; None (an empty
+        state, where the call takes one) -> (None, None, None, P)."""
+        if state is None and not required:
+            return None, None, None, P
+        if not isinstance(state, (tuple, list)) or len(state) != 3 or not isinstance(state[0], torch.Tensor):
+            raise ValueError(f"{what}: state must be (count [P] int64, mean [P, {self.D}], m2 [P, {self.D}])"
+                             f"{'' if required else ' or None'}, got {type(state)}")
+        count, mean, m2 = state
+        if P is None:
+            P = int(count.shape[0]) if count.dim() == 1 else 0
+            if P < 1:
+                raise ValueError(f"{what}: state: count must be an int64 tensor [P] with P >= 1, got {tuple(count.shape)}")
+        self._outs(what, ((count, (P,), torch.int64, "state: count"), (mean, (P, self.D), None, "state: mean"),
+                          (m2, (P, self.D), None, "state: m2")))
+        if mean is None or m2 is None:
+            raise ValueError(f"{what}: state: count, mean and m2 go together")
+        return count, mean, m2, P
+
+    def obs_stats_into(self, obs, count, mean, m2, lane_sum, lane_count, *, policies: int = 1, obs0=None, length=None, state=None,
+                       steps=None, valid=None):
+        """Allocation-free merge of one batch of observations into the running mean and deviation of P = policies policies, on
+        tensors in the kernel's layouts (include/os2r_norm.h: os2rz_obs_stats; the arithmetic and its order are spelled out
+        there).  With S samples, N = S P lanes (lane s P + p: sample s of policy p) and K steps: obs [K, N, D], obs0 [N, D]
+        (None: obs[k] is what step k's action saw), length [N] int32 (None: K) and state = (count [P] int64, mean [P, D],
+        m2 [P, D]) (None: empty) are read; count [P] int64, mean [P, D], m2 [P, D], lane_sum [2 D, N] and lane_count [2, N] int32
+        (all five required: the second launch reads what the first wrote into the last two) and steps, valid [P] int32 (each or
+        None) are written.  An output may not overlap an input: the caller swaps two states.  Shapes, dtypes, device, contiguity
+        and overlap are checked before the library is called (it takes addresses)."""
+        what = "obs_stats"
+        K, N, S, P = self._pg_lanes(what, obs, policies)
+        c_in, m_in, q_in, _ = self._norm_state(what, state, P, required=False)
+        if any(t is None for t in (count, mean, m2, lane_sum, lane_count)):
+            raise ValueError(f"{what}: obs, count, mean, m2, lane_sum and lane_count are required")
+        D, i32, i64 = self.D, torch.int32, torch.int64
+        inputs = ((obs, (K, N, D), None, "obs"), (obs0, (N, D), None, "obs0"), (length, (N,), i32, "length"),
+                  (c_in, (P,), i64, "state: count"), (m_in, (P, D), None, "state: mean"), (q_in, (P, D), None, "state: m2"))
+        outputs = ((count, (P,), i64, "count"), (mean, (P, D), None, "mean"), (m2, (P, D), None, "m2"), (steps, (P,), i32, "steps"),
+                   (valid, (P,), i32, "valid"), (lane_sum, (2 * D, N), None, "lane_sum"), (lane_count, (norm.LANE_COUNTS, N), i32, "lane_count"))
+        self._outs(what, inputs + outputs)
+        self._no_overlap(what, inputs, outputs)
+        _call(norm, "os2rz_obs_stats", "os2rz_last_error", C.byref(self._layout()), K, P, S, 0, _ptr(obs), _ptr(obs0), _ptr(length),
+              _ptr(c_in), _ptr(m_in), _ptr(q_in), _ptr(count), _ptr(mean), _ptr(m2), _ptr(steps), _ptr(valid), _ptr(lane_sum),
+              _ptr(lane_count), self._stream())
+
+    def obs_stats(self, obs, *, policies: int = 1, obs0=None, length=None, state=None):
+        """The running mean and deviation of every observation component of P = policies policies after one more batch, in one
+        call (include/os2r_norm.h: os2rz_obs_stats): obs [K, N, D] and length [N] int32 are what
+        rollout_policy(want_outputs=True) returned, obs0 [N, D] what reset() or the previous window's last step returned (None:
+        obs[k] is what step k saw), all taken without a copy; lane s P + p is sample s of policy p.  state is None (nothing seen
+        yet) or the (count [P] int64, mean [P, D], m2 [P, D]) an earlier call returned: m2 is the sum of squared deviations, so
+        the variance is m2 / count.  The batch's sums are taken about the running mean (or, for an empty state, about the first
+        observation), which keeps float32 exact where a component's mean is large beside its deviation, and merged by Chan's
+        formula.  A lane one of whose sums is not finite is left out; a policy without a counted step keeps its state.
+        -> (state: new tensors, the one given is left as it is; steps [P] int32: the counted steps of the batch; valid [P]
+        int32: the valid lanes).  norm_fold(theta, state) gives the weights rollout_policy takes for a policy theta on whitened
+        observations, norm_unfold(grad, state) takes a gradient back."""
+        what = "obs_stats"
+        K, N, S, P = self._pg_lanes(what, obs, policies)                    # (here too: they size what is allocated)
+        D, i32 = self.D, torch.int32
+        count, mean, m2 = self._new(P, dtype=torch.int64), self._new(P, D), self._new(P, D)
+        steps, valid = self._new(P, dtype=i32), self._new(P, dtype=i32)
+        self.obs_stats_into(obs, count, mean, m2, self._new(2 * D, N), self._new(norm.LANE_COUNTS, N, dtype=i32), policies=P, obs0=obs0,
+                            length=length, state=state, steps=steps, valid=valid)
+        return (count, mean, m2), steps, valid
+
+    def _norm_sets(self, what, t, name, Q=None):
+        """theta, weights or a gradient of the allocating whitening calls, [Q, rows, D+1] or [Q, D+1] (one row: value weights) ->
+        (the tensor as the kernel takes it, policy_fastest, the function that gives a kernel tensor the caller's shape back).  A
+        permuted view of the kernel's [rows, D+1, Q] (what policy_gradient and value_fit return) goes on without a copy."""
+        n = self.D + 1
+        if not isinstance(t, torch.Tensor) or t.dim() not in (2, 3) or t.shape[-1] != n or t.shape[0] < 1 or (t.dim() == 3 and t.shape[1] not in (1, 2)):
+            raise ValueError(f"{what}: {name} must be a tensor [Q, 2, {n}], [Q, 1, {n}] or [Q, {n}] with Q >= 1, got "
+                             f"{tuple(getattr(t, 'shape', ())) or type(t)}")
+        if t.dtype != self.dtype or t.device != self.device:
+            raise ValueError(f"{what}: {name} must be {self.dtype} on {self.device}, got {t.dtype} on {t.device}")
+        if Q is not None and int(t.shape[0]) != Q:
+            raise ValueError(f"{what}: {name} must hold {Q} sets, got {int(t.shape[0])}")
+        flat = t.dim() == 2
+        full = t.unsqueeze(1) if flat else t                              # [Q, rows, D+1]
+        if not full.is_contiguous() and full.permute(1, 2, 0).is_contiguous():
+            back = (lambda k: k.permute(2, 0, 1).squeeze(1)) if flat else (lambda k: k.permute(2, 0, 1))
+            return full.permute(1, 2, 0), True, back
+        return full.contiguous(), False, ((lambda k: k.squeeze(1)) if flat else (lambda k: k))
+
+    def _norm_call(self, what, entry, source, state, out, std_floor, lanes, policy_fastest, names):
+        """What norm_fold_into and norm_unfold_into share: the checks of the state, the scale and the two arrays, and the call."""
+        count, mean, m2, P = self._norm_state(what, state)
+        floor = _finite(what, "std_floor", math.nan if isinstance(std_floor, bool) else std_floor, lambda x: x > 0.0, "> 0", repr(std_floor))
+        if self.dtype == torch.float32 and float(torch.tensor(floor, dtype=torch.float32)) == 0.0:
+            raise ValueError(f"{what}: std_floor must be finite and > 0 in float32, got {std_floor!r}")
+        Q = P
+        if lanes is not None:
+            Q = _count(what, "lanes", lanes)
+            _split(what, Q, P, "lanes", "policies")
+            if Q > 2 ** 31 - 1:
+                raise ValueError(f"{what}: {Q} lanes exceed what an int32 holds")
+        if source is None or out is None:
+            raise ValueError(f"{what}: {names[0]} and {names[1]} are required")
+        n = self.D + 1
+        fastest = bool(policy_fastest)
+        if not isinstance(source, torch.Tensor) or source.dim() != 3 or source.shape[0 if fastest else 1] not in (1, 2):
+            raise ValueError(f"{what}: {names[0]} must be a tensor [{Q}, rows, {n}], or [rows, {n}, {Q}] with policy_fastest, rows 1 or 2, "
+                             f"got {tuple(getattr(source, 'shape', ())) or type(source)}")
+        rows = int(source.shape[0 if fastest else 1])
+        shape = (rows, n, Q) if fastest else (Q, rows, n)
+        inputs = ((count, (P,), torch.int64, "state: count"), (mean, (P, self.D), None, "state: mean"), (m2, (P, self.D), None, "state: m2"),
+                  (source, shape, None, names[0]))
+        outputs = ((out, shape, None, names[1]),)
+        self._outs(what, inputs + outputs)
+        self._no_overlap(what, inputs, outputs)
+        flags = (norm.POLICY_FASTEST if fastest else 0) | (norm.PER_LANE if lanes is not None else 0)
+        head = (C.byref(self._layout()), P) + ((Q,) if entry == "os2rz_fold" else ()) + (rows, flags)
+        _call(norm, entry, "os2rz_last_error", *head, _ptr(count), _ptr(mean), _ptr(m2), floor, _ptr(source), _ptr(out), self._stream())
+
+    def norm_fold_into(self, theta, state, weights, *, std_floor: float = 1e-6, lanes=None, policy_fastest: bool = False):
+        """Allocation-free fold of policies given on whitened observations into weights on raw ones, in one launch, on tensors in
+        the kernel's layouts (include/os2r_norm.h: os2rz_fold; the arithmetic is spelled out there).  state = (count [P] int64,
+        mean [P, D], m2 [P, D]) as obs_stats returns it and theta are read, weights is written; both are [Q, rows, D+1] or, with
+        policy_fastest, [rows, D+1, Q], rows 2 for a policy or 1 for value weights.  Q = P, set p under the statistics of policy
+        p; with lanes = N (a multiple of P) Q = N, set l under those of policy l mod P -- what es_perturb writes and what the
+        per-environment rollout_policy reads.  std_floor > 0 bounds the deviation from below.  A policy with count < 2 is copied
+        through.  Shapes, dtypes, device, contiguity and overlap are checked before the library is called (it takes addresses)."""
+        self._norm_call("norm_fold", "os2rz_fold", theta, state, weights, std_floor, lanes, policy_fastest, ("theta", "weights"))
+
+    def norm_fold(self, theta, state, *, std_floor: float = 1e-6, lanes=None):
+        """The weights W, b with W . x + b = theta . [(x - mean) / std; 1], in one launch (include/os2r_norm.h: os2rz_fold): theta
+        [P, 2, D+1] holds P policies on whitened observations (or [P, D+1]: value weights, one row), state is what obs_stats
+        returned, std = max(sqrt(m2 / count), std_floor).  With lanes = N theta is [N, 2, D+1], one set per lane as es_perturb
+        returns it, lane l under the statistics of policy l mod P.  A permuted view of the kernel's [rows, D+1, Q] layout (a
+        gradient-shaped tensor, or value_fit's weights) is taken without a copy and the result has the same layout, so it goes
+        into rollout_policy or gae as it is.  A policy that has seen fewer than two observations is returned unchanged.
+        -> weights, shaped like theta."""
+        what = "norm_fold"
+        _, _, _, P = self._norm_state(what, state)
+        Q = P if lanes is None else _count(what, "lanes", lanes)
+        source, fastest, back = self._norm_sets(what, theta, "theta", Q)
+        out = torch.empty_like(source)
+        self.norm_fold_into(source, state, out, std_floor=std_floor, lanes=lanes, policy_fastest=fastest)
+        return back(out)
+
+    def norm_unfold_into(self, grad, state, grad_theta, *, std_floor: float = 1e-6, policy_fastest: bool = False):
+        """Allocation-free chain rule back through norm_fold, in one launch, on tensors in the kernel's layouts
+        (include/os2r_norm.h: os2rz_unfold): grad, the gradient with respect to the folded weights, is read and grad_theta, the
+        gradient with respect to theta, is written; both are [P, rows, D+1] or, with policy_fastest, [rows, D+1, P] -- the layout
+        policy_gradient_into and ppo_gradient_into write.  state and std_floor are those of the fold.  Shapes, dtypes, device,
+        contiguity and overlap are checked before the library is called (it takes addresses)."""
+        self._norm_call("norm_unfold", "os2rz_unfold", grad, state, grad_theta, std_floor, None, policy_fastest, ("grad", "grad_theta"))
+
+    def norm_unfold(self, grad, state, *, std_floor: float = 1e-6):
+        """The gradient with respect to theta of a function of the weights norm_fold(theta, state) gave, from its gradient with
+        respect to those weights, in one launch (include/os2r_norm.h: os2rz_unfold): grad [P, 2, D+1] as policy_gradient or
+        ppo_gradient return it (their permuted view of the kernel's layout is taken without a copy), or [P, D+1].
+        gtheta[j, d] = (g[j, d] - g[j, D] mean_d) / std_d, gtheta[j, D] = g[j, D].  A step (natural_step's) is not a gradient
+        and is not mapped: the natural gradient is invariant under the reparametrisation.
+        -> grad_theta, shaped like grad."""
+        what = "norm_unfold"
+        _, _, _, P = self._norm_state(what, state)
+        source, fastest, back = self._norm_sets(what, grad, "grad", P)
+        out = torch.empty_like(source)
+        self.norm_unfold_into(source, state, out, std_floor=std_floor, policy_fastest=fastest)
+        return back(out)
