@@ -4,6 +4,7 @@ by side towards a target posture, the backward pass in one os2rc_ilqr_backward l
 
   python examples/ilqr_balancing.py [--envs 64] [--steps 40] [--iters 10] [--settle 300] [--perturb 0.05] [--mu 0.0] [--eps 1e-4]
                                     [--knots recorded|loop] [--line-search torch|device|steered] [--armijo 0] [--tol 0] [--poll P]
+                                    [--box] [--timing]
 
 The cost of a trajectory is sum_k 1/2 (x_k - x*)'Q(x_k - x*) + 1/2 a_k'R a_k plus 1/2 (x_K - x*)'Q(x_K - x*), read off the raw
 observation slots (state components the task does not observe carry no weight); x* is the posture the PD of lqr_balancing.py
@@ -46,7 +47,12 @@ once, and prints the mean cost, the histogram of mu and how many trajectories ar
 trajectories still run through the backward pass and the rollout; they are just never accepted.
 Printed per iteration: the cost (mean over the trajectories), the step size, mu, the refused knots, and the predicted against
 the actual change.  The script prints what happened; it claims no control quality: a quotient across a change of contact mode
-is a secant, the default eps is not tuned, and the actions saturate, which the model knows nothing about.
+is a secant, the default eps is not tuned, and the actions saturate, which the model knows nothing about -- unless --box is given.
+With --box, in all three --line-search modes, the backward pass is the control-limited one (ilqr_backward(box=True):
+os2rb_ilqr_backward_box): where the step of the unconstrained model would leave [-1, 1] it is the exact minimum on the box, the
+feedback row of a clamped actuator is zero, and the value recursion sees both.  Every printed line of an iteration then ends with
+the share of knots at which a component is clamped (steered: of the iteration that was polled).  --timing (steered) adds the wall
+time per iteration of the whole loop, read after the last poll.
 """
 import argparse
 import os
@@ -60,6 +66,19 @@ from gym_os2r_amd.control import slot_columns
 from lqr_balancing import weights_of_gain
 
 ALPHAS = (1.0, 0.5, 0.25, 0.125)
+
+
+def backward(sim, box, *args, **kw):
+    """sim.ilqr_backward, with --box the control-limited pass -> (its seven results, clamped [K, M] uint8 or None)"""
+    if not box:
+        return sim.ilqr_backward(*args, **kw), None
+    out = sim.ilqr_backward(*args, box=True, **kw)
+    return out[:7], out[7]
+
+
+def clamped_share(clamped):
+    """the end of a printed line: nothing without --box"""
+    return "" if clamped is None else f"; clamped {float((clamped != 0).double().mean()):.3f} of the knots"
 
 
 def main():
@@ -84,6 +103,8 @@ def main():
     ap.add_argument("--armijo", type=float, default=0.0, help="steered: a step must lower the cost by this times the predicted change")
     ap.add_argument("--tol", type=float, default=0.0, help="steered: a trajectory converges when a step lowers its cost by no more than tol |cost|")
     ap.add_argument("--poll", type=int, default=0, help="steered: read the device every P iterations (0: only after the last)")
+    ap.add_argument("--box", action="store_true", help="the control-limited backward pass: steps inside [-1, 1], clamped feedback rows zero")
+    ap.add_argument("--timing", action="store_true", help="steered: print the wall time per iteration after the last poll")
     args = ap.parse_args()
     M, K, nal = args.envs, args.steps, len(ALPHAS)
     recorded = args.knots == "recorded"
@@ -177,8 +198,9 @@ def main():
         p_final = torch.zeros(M, n, dtype=dt, device=dev)
         p_final[:, shown] = qs * (end_obs[:, slots] - target)
         # 4. the backward pass and the candidates' table in one launch
-        _, _, _, _, flags, dv, table = nom.ilqr_backward(A, B, Q.cpu(), R.cpu(), knots=K, lx=lx, lu=lu, mu=mu, p_final=p_final, actions=a_k,
-                                                         obs=obs_k, alphas=ALPHAS, want_gains=False, want_ff=False, want_weights=True)
+        (_, _, _, _, flags, dv, table), clamped = backward(nom, args.box, A, B, Q.cpu(), R.cpu(), knots=K, lx=lx, lu=lu, mu=mu, p_final=p_final,
+                                                           actions=a_k, obs=obs_k, alphas=ALPHAS, want_gains=False, want_ff=False,
+                                                           want_weights=True)
         refused = int(flags.sum())
         # 5. all candidates of all trajectories in one launch, from knot 0
         cand.copy_envs_from(knots, first)
@@ -199,8 +221,8 @@ def main():
             actual = float((J_c[best] - J).mean())
             shown_cost = float(J_c[best].mean())
             print(f"iter {it:2d} cost {shown_cost:.6e} alpha {alpha:5.3f} mu {mu:.3e} refused {refused} of {K * M} knots, predicted change "
-                  f"{predicted:+.4e} actual {actual:+.4e}; {int((d_c.view(K, nal, M)[:, best] != 0).any(0).sum())} of {M} episodes ended",
-                  flush=True)
+                  f"{predicted:+.4e} actual {actual:+.4e}; {int((d_c.view(K, nal, M)[:, best] != 0).any(0).sum())} of {M} episodes ended"
+                  + clamped_share(clamped), flush=True)
             U = a_c.view(K, nal, M, 2)[:, best].contiguous()
             if recorded:
                 # the accepted candidate is the new nominal: its knots in one launch, its observations as they were recorded
@@ -210,7 +232,7 @@ def main():
             mu = 0.5 * mu if mu > 1e-3 else 0.0
         else:
             print(f"        no step size lowers the cost at mu {mu:.3e} (best alpha {ALPHAS[best]}: {float(total[best] - J.sum()) / M:+.4e}, "
-                  f"refused {refused} of {K * M} knots): mu raised", flush=True)
+                  f"refused {refused} of {K * M} knots): mu raised" + clamped_share(clamped), flush=True)
             mu = max(10.0 * mu, 0.1)
     while it < args.iters:                                                            # (kept: every iteration has its line)
         it += 1
@@ -238,9 +260,9 @@ def line_search_on_device(args, nom, knots, cand, cand_knots, start, target, Q, 
     while it < args.iters and tries < 4 * args.iters:
         tries += 1
         _, _, A, B = knots.linearize(a_k, args.eps, want_next=False)
-        _, _, _, _, flags, dv, table = nom.ilqr_backward(A, B, Q, R, knots=K, lx=nominal["lx_view"], lu=nominal["lu_view"], mu=mu,
-                                                         p_final=nominal["p_final_view"], actions=a_k, obs=obs_k, alphas=ALPHAS,
-                                                         want_gains=False, want_ff=False, want_weights=True)
+        (_, _, _, _, flags, dv, table), clamped = backward(nom, args.box, A, B, Q, R, knots=K, lx=nominal["lx_view"], lu=nominal["lu_view"],
+                                                           mu=mu, p_final=nominal["p_final_view"], actions=a_k, obs=obs_k, alphas=ALPHAS,
+                                                           want_gains=False, want_ff=False, want_weights=True)
         cand.copy_envs_from(knots, first)
         _, _, (o_c, _, d_c, _, _), (a_c, _), kobs_c = cand.rollout_schedule(K, table, want_outputs=True, want_actions=True,
                                                                           knots=cand_knots, want_knot_obs=True)
@@ -258,10 +280,11 @@ def line_search_on_device(args, nom, knots, cand, cand_knots, start, target, Q, 
             actual = float((nominal["cost"] - before).sum()) / M
             steps = ", ".join(f"{took[i + 1]} x {ALPHAS[i]}" for i in range(nal))
             print(f"iter {it:2d} cost {float(nominal['cost'].mean()):.6e} step sizes {steps}, none {took[0]}; mu {mu:.3e} refused {refused} of "
-                  f"{K * M} knots, predicted change {predicted:+.4e} actual {actual:+.4e}", flush=True)
+                  f"{K * M} knots, predicted change {predicted:+.4e} actual {actual:+.4e}" + clamped_share(clamped), flush=True)
             mu = 0.5 * mu if mu > 1e-3 else 0.0
         else:
-            print(f"        no trajectory accepted a step size at mu {mu:.3e} (refused {refused} of {K * M} knots): mu raised", flush=True)
+            print(f"        no trajectory accepted a step size at mu {mu:.3e} (refused {refused} of {K * M} knots): mu raised"
+                  + clamped_share(clamped), flush=True)
             mu = max(10.0 * mu, 0.1)
     while it < args.iters:                                                            # (kept: every iteration has its line)
         it += 1
@@ -284,11 +307,15 @@ def steered_on_device(args, nom, knots, cand, cand_knots, start, target, Q, R, f
           f"had an episode end inside it and stay out)", flush=True)
     a_k, obs_k = nominal["actions"].view(K * M, 2), nominal["obs"].view(K * M, D)        # views: updated in place by every call
     edges = (0.0, 1e-3, 1e-1, 1e1, 1e3)
+    if args.timing:
+        import time
+        torch.cuda.synchronize()
+        began = time.perf_counter()
     for it in range(1, args.iters + 1):
         _, _, A, B = knots.linearize(a_k, args.eps, want_next=False)
-        _, _, _, _, _, dv, table = nom.ilqr_backward(A, B, Q, R, knots=K, lx=nominal["lx_view"], lu=nominal["lu_view"], mu_dev=nominal["mu"],
-                                                     p_final=nominal["p_final_view"], actions=a_k, obs=obs_k, alphas=ALPHAS,
-                                                     want_gains=False, want_ff=False, want_flags=False, want_weights=True)
+        (_, _, _, _, _, dv, table), clamped = backward(nom, args.box, A, B, Q, R, knots=K, lx=nominal["lx_view"], lu=nominal["lu_view"],
+                                                       mu_dev=nominal["mu"], p_final=nominal["p_final_view"], actions=a_k, obs=obs_k,
+                                                       alphas=ALPHAS, want_gains=False, want_ff=False, want_flags=False, want_weights=True)
         cand.copy_envs_from(knots, first)
         _, _, (o_c, _, d_c, _, _), (a_c, _), kobs_c = cand.rollout_schedule(K, table, want_outputs=True, want_actions=True,
                                                                           knots=cand_knots, want_knot_obs=True)
@@ -303,7 +330,10 @@ def steered_on_device(args, nom, knots, cand, cand_knots, start, target, Q, R, f
             state = torch.bincount(status, minlength=3).tolist()
             print(f"iter {it:2d} cost {float(cost.mean()):.6e} mu " + ", ".join(f"{c} x {nm}" for c, nm in zip(hist, names)) +
                   f"; active {state[0]} converged {state[1]} stalled {state[2]}; accepted steps per trajectory {int(iters.min())}.."
-                  f"{int(iters.max())}", flush=True)
+                  f"{int(iters.max())}" + clamped_share(clamped), flush=True)
+    if args.timing:
+        torch.cuda.synchronize()
+        print(f"time per iteration {1e3 * (time.perf_counter() - began) / max(args.iters, 1):.3f} ms (wall, polls included)", flush=True)
 
 
 if __name__ == "__main__":

@@ -1,4 +1,5 @@
-"""The controller calls of a HipSim: LQR gains, the iLQR backward pass, its line search with and without a steered mu, the MPPI
+"""The controller calls of a HipSim: LQR gains, the iLQR backward pass (plain, with a mu per trajectory, or under box limits on the
+actions), its line search with and without a steered mu, the MPPI
 update, the cross-entropy update, the particle-filter update, the Kalman filter update, the two calls of the unscented Kalman filter (its sigma points and its update), the
 score-function policy gradient, the two calls of the critic (GAE(lambda) and the linear value fit), the clipped-surrogate (PPO) gradient, the natural-gradient step, the two calls of evolution-strategy search (the perturbation and the ARS update) and the three of running observation whitening (the statistics, the fold and the gradient back), each as an allocation-free ``*_into`` on tensors in the kernel's layout and an allocating
 wrapper around it.  ``Controllers`` is the plain base class HipSim (gym_os2r_amd.sim) inherits them from; it uses the handle's
@@ -15,7 +16,7 @@ import math
 
 import torch
 
-from . import abi, cem, control, critic, ekf, es, mppi, norm, npg, pf, pg, ppo, search, steer, ukf
+from . import abi, box as box_lib, cem, control, critic, ekf, es, mppi, norm, npg, pf, pg, ppo, search, steer, ukf
 from ._lib import Os2rError, _ptr
 
 NOMINAL_KEYS = ("cost", "actions", "obs", "end_obs", "lx", "lu", "p_final")
@@ -223,15 +224,19 @@ class Controllers:
 
     def ilqr_backward_into(self, A, B, Q, R, *, knots: int = 1, lx=None, lu=None, mu: float = 0.0, P_final=None, p_final=None,
                            gains_out=None, ff_out=None, P_out=None, p_out=None, flags_out=None, dv_out=None, actions=None, obs=None,
-                           alphas=None, weights_out=None, mu_dev=None):
+                           alphas=None, weights_out=None, mu_dev=None, box=None, clamp_out=None):
         """Allocation-free variant of ilqr_backward() on tensors in the kernel's layout (include/os2r_control.h:
         os2rc_ilqr_backward), the trajectory index fastest: with K = knots, L = K M and n = 2nq, A [n, n, L], B [n, 2, L],
         lx [n, L], lu [2, L], P_final [n, n, M], p_final [n, M] (each of the four None for its default), gains_out [K, 2, n, M],
         ff_out [K, 2, M], P_out [n, n, M] (may be P_final), p_out [n, M] (may be p_final), flags_out [K, M] uint8,
         dv_out [K, 2, M], weights_out [K, 2, D+1, len(alphas) M] with actions [L, 2], obs [L, D] and alphas; each output may be
         None, not all of them but flags_out.  mu_dev [M]: one mu per trajectory, read on the device (include/os2r_steer.h:
-        os2rt_ilqr_backward_mu; mu itself must then be 0).  Shapes, dtypes, device and contiguity are checked before the library is
-        called (it takes addresses)."""
+        os2rt_ilqr_backward_mu; mu itself must then be 0).  box: None, or True for (-1, 1), or (lo, hi), each a number or a pair of
+        numbers, lo -inf or finite in [-1, 1], hi +inf or finite in [-1, 1]: the feed-forward step stays inside the box around the
+        clamped nominal, the feedback rows of the clamped components are zero and the value recursion sees both
+        (include/os2r_box.h: os2rb_ilqr_backward_box); actions [L, 2] is then required, and clamp_out [K, M] uint8 (or None) takes
+        the knots' clamp bytes.  Shapes, dtypes, device and contiguity are checked before the library is called (it takes
+        addresses)."""
         what = "ilqr_backward"
         n = 2 * self.nq
         K = int(knots)
@@ -247,29 +252,42 @@ class Controllers:
         if mu_dev is not None and mu != 0.0:
             raise ValueError(f"{what}: mu_dev and a nonzero mu ({mu}) are both given; the regularisation is one or the other")
         self._out(mu_dev, (M,), self.dtype, f"{what}: mu_dev")
+        if box is None or box is False:
+            box = None
+            if clamp_out is not None:
+                raise ValueError(f"{what}: clamp_out is written by the box-limited pass only (box=...)")
+        else:
+            lo, hi = box_lib.bounds(box, what)
+            if actions is None:
+                raise ValueError(f"{what}: box needs actions (the bounds are relative to the nominal actions)")
         if B is None:
             raise ValueError(f"{what}: B is required")
         nal = 0 if al is None else len(al)
         if weights_out is None:
-            actions = obs = None
+            obs = None
+            if box is None:
+                actions = None
         self._outs(what, ((A, (n, n, L), None, "A"), (B, (n, 2, L), None, "B"), (lx, (n, L), None, "lx"), (lu, (2, L), None, "lu"),
                           (P_final, (n, n, M), None, "P_final"), (p_final, (n, M), None, "p_final"),
                           (gains_out, (K, 2, n, M), None, "gains_out"), (ff_out, (K, 2, M), None, "ff_out"), (P_out, (n, n, M), None, "P_out"),
                           (p_out, (n, M), None, "p_out"), (dv_out, (K, 2, M), None, "dv_out"), (flags_out, (K, M), torch.uint8, "flags_out"),
                           (weights_out, (K, 2, self.D + 1, nal * M), None, "weights_out"), (actions, (L, 2), None, "actions"),
-                          (obs, (L, self.D), None, "obs")))
-        # the two entry points differ in the regularisation alone: a host value, or one per trajectory read on the device
+                          (obs, (L, self.D), None, "obs"), (clamp_out, (K, M), torch.uint8, "clamp_out")))
+        # the entry points differ in the regularisation: a host value, or one per trajectory read on the device
         head = (C.byref(self._layout()), K, M, _ptr(A), _ptr(B), _ptr(lx), _ptr(lu), q, r)
         tail = (_ptr(P_final), _ptr(p_final), _ptr(gains_out), _ptr(ff_out), _ptr(P_out), _ptr(p_out), _ptr(flags_out), _ptr(dv_out),
                 _ptr(actions), _ptr(obs), al, nal, _ptr(weights_out), self._stream())
-        if mu_dev is None:
+        if box is not None:        # ... and in the box: that entry point takes both forms of mu, and the clamp bytes
+            _call(box_lib, "os2rb_ilqr_backward_box", "os2rb_last_error", *head, mu, _ptr(mu_dev), lo, hi, *tail[:8], _ptr(clamp_out),
+                  *tail[8:])
+        elif mu_dev is None:
             _call(control, "os2rc_ilqr_backward", "os2rc_last_error", *head, mu, *tail)
         else:
             _call(steer, "os2rt_ilqr_backward_mu", "os2rt_last_error", *head, _ptr(mu_dev), *tail)
 
     def ilqr_backward(self, A, B, Q, R, *, knots, lx=None, lu=None, mu=0.0, P_final=None, p_final=None, actions=None, obs=None,
                       alphas=None, want_gains=True, want_ff=True, want_P=False, want_p=False, want_flags=True, want_dv=True,
-                      want_weights=False, mu_dev=None):
+                      want_weights=False, mu_dev=None, box=None):
         """The backward pass of iLQR for M = L / knots independent trajectories in one launch (include/os2r_control.h:
         os2rc_ilqr_backward; the arithmetic and its order are spelled out there): lqr_gains(sweeps=1) with its affine terms.
         A [L, 2nq, 2nq] and B [L, 2nq, 2] as linearize() returns them (taken without a copy), lane k * M + m knot k of trajectory
@@ -284,7 +302,13 @@ class Controllers:
         handle of len(alphas) M environments, environment i M + m being trajectory m under alphas[i].
         mu_dev [M] (the handle's dtype, on its device, contiguous; mu must then be 0): one mu per trajectory, read on the device
         -- the array ilqr_steer keeps up to date.  Trajectory m gets what mu = mu_dev[m] gives it, bit for bit; a negative or
-        non-finite entry runs as 0 with every knot of that trajectory refused (include/os2r_steer.h: os2rt_ilqr_backward_mu)."""
+        non-finite entry runs as 0 with every knot of that trajectory refused (include/os2r_steer.h: os2rt_ilqr_backward_mu).
+        box: True for (-1, 1), or (lo, hi), each a number or a pair of numbers: the control-limited pass
+        (include/os2r_box.h: os2rb_ilqr_backward_box).  Per knot the feed-forward step is the exact minimum of the model over
+        lo <= a_k + ff_k <= hi (a_k clamped to [-1, 1]), the gain rows of the clamped components are zero and the value
+        recursion sees both; actions is then required even without want_weights, and the result gains a last member
+        clamped [K, M] uint8: bit c set where component c is held at a bound, bit 2 + c where that is the upper one.  Without
+        box nothing changes."""
         what = "ilqr_backward"
         n = 2 * self.nq
         K = int(knots)
@@ -293,6 +317,11 @@ class Controllers:
         if want_weights and (actions is None or obs is None or alphas is None):      # (here too: the table is sized by the alphas)
             raise ValueError(f"{what}: weights need actions, obs (the point each knot was linearised about) and alphas")
         al = self._ilqr_scalars(mu, alphas, want_weights)[1]
+        boxed = box is not None and box is not False
+        if boxed:                                     # (here too: before anything is permuted, copied or allocated)
+            box_lib.bounds(box, what)
+            if actions is None:
+                raise ValueError(f"{what}: box needs actions (the bounds are relative to the nominal actions)")
         a, b, L, M = self._riccati_views(what, A, B, K)
 
         def given(t, shape, name, perm):
@@ -312,6 +341,9 @@ class Controllers:
         if want_weights:
             nal = len(al)
             act, ob = given(actions, (L, 2), "actions", (0, 1)), given(obs, (L, self.D), "obs", (0, 1))
+        elif boxed:
+            act = given(actions, (L, 2), "actions", (0, 1))
+        clamped = self._new(K, M, dtype=torch.uint8) if boxed else None
         gains = self._new(K, 2, n, M) if want_gains else None
         ff = self._new(K, 2, M) if want_ff else None
         pout = self._new(n, n, M) if want_P else None
@@ -320,10 +352,12 @@ class Controllers:
         dv = self._new(K, 2, M) if want_dv else None
         wts = self._new(K, 2, self.D + 1, nal * M) if want_weights else None
         self.ilqr_backward_into(a, b, Q, R, knots=K, lx=gx, lu=gu, mu=mu, P_final=pfin, p_final=vf, gains_out=gains, ff_out=ff, P_out=pout,
-                                p_out=vout, flags_out=flags, dv_out=dv, actions=act, obs=ob, alphas=alphas, weights_out=wts, mu_dev=mu_dev)
-        return (gains.permute(0, 3, 1, 2) if want_gains else None, ff.permute(0, 2, 1) if want_ff else None,
-                pout.permute(2, 0, 1) if want_P else None, vout.permute(1, 0) if want_p else None, flags,
-                dv.permute(0, 2, 1) if want_dv else None, wts.permute(3, 0, 1, 2) if want_weights else None)
+                                p_out=vout, flags_out=flags, dv_out=dv, actions=act, obs=ob, alphas=alphas, weights_out=wts, mu_dev=mu_dev,
+                                box=box if boxed else None, clamp_out=clamped)
+        out = (gains.permute(0, 3, 1, 2) if want_gains else None, ff.permute(0, 2, 1) if want_ff else None,
+               pout.permute(2, 0, 1) if want_P else None, vout.permute(1, 0) if want_p else None, flags,
+               dv.permute(0, 2, 1) if want_dv else None, wts.permute(3, 0, 1, 2) if want_weights else None)
+        return out + (clamped,) if boxed else out
 
     # -- iLQR line search, plain and steering mu ----------------------------------------------
     def _search_cost(self, what, Q, R, Q_final):

@@ -21,6 +21,9 @@
 //
 // The arithmetic is the contract of include/os2r_control.h: the layout's dtype, no contraction, every sum of products
 // ((x0 y0 + x1 y1) + x2 y2) + ... with the index ascending.  tests/test_gpu_ilqr_backward.py restates it in numpy, bit for bit.
+//
+// os2r_ilqr_mu.hpp (one mu per trajectory) and os2r_ilqr_box.hpp (that, with the box QP in phase 2a) hold copies of this text,
+// against the rule of DESIGN.md section 4; the first says why.  Whoever changes one of the three texts changes the others.
 #pragma once
 #include "os2r_lqr.hpp"
 #include "../../include/os2r_control.h"

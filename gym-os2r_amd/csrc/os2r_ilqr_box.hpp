@@ -1,37 +1,39 @@
-// os2r_ilqr_mu.hpp — os2rt_ilqr_backward_mu: the backward pass of iLQR with one regularisation mu per trajectory (gfx950).
+// os2r_ilqr_box.hpp — os2rb_ilqr_backward_box: the backward pass of iLQR whose feed-forward step stays inside a box around the
+// nominal action, one regularisation mu per trajectory or one for all (gfx950).
 //
-// The kernel is ilqr_backward_kernel of os2r_ilqr.hpp -- the same lane layout (32 trajectories x (n + 2) columns, P, A, B, G, K
-// in LDS), the same phases, the same operations in the same order -- with two differences:
-//   mu       every lane loads its trajectory's mu once, into a register; where the kernel of os2r_ilqr.hpp branches on the
-//            argument mu != 0 (T = S + mu, the last terms of steps 7 and 8), this one selects per lane: a lane whose mu is 0
-//            keeps S, P' and p' as they are and never adds a zero, so every trajectory gets the bits os2rc_ilqr_backward gives
-//            it when called with its mu.  A mu that is negative or not finite (on its bit pattern: the host cannot look) runs
-//            as 0 with every knot of the trajectory refused.
-//   barrier  the one between phases 2a and 2b is always taken: it must be uniform over the workgroup, and neighbouring
-//            trajectories differ in whether they need the K of the other columns.
-// No lane indexes a register array at run time, nothing goes to scratch (tests/test_ilqr_steer_host.py reads the metadata).
+// The kernel is ilqr_backward_mu_kernel of os2r_ilqr_mu.hpp -- the same lane layout (32 trajectories x (n + 2) columns, P, A, B,
+// G, K in LDS), the same prefetch, the same phases and barriers, the same operations in the same order -- with these differences:
+//   mu       from the array, or, where that is null, the argument of os2rc_ilqr_backward: a uniform choice made once
+//   actions  a column lane reads the two nominal actions of its trajectory's knot, prefetched with the next column
+//   phase 2a after K and k of the interior, as there, every column lane solves the box QP of include/os2r_box.h (B1-B4) for
+//            itself, as it forms k for itself: four edge candidates by selects, never by a branch that diverges (neighbouring
+//            trajectories differ in their active set).  A wave none of whose trajectories leaves the box skips the candidates:
+//            that branch is uniform, and what it skips is only ever selected by a lane that left the box.  Lane c == 0 writes
+//            the clamp byte next to the flag.
+// No lane indexes a register array at run time, nothing goes to scratch (tests/test_ilqr_box_host.py reads the metadata).
 //
-// The arithmetic is the contract of include/os2r_control.h, steps 1-10, with mu read per trajectory (include/os2r_steer.h).
+// The arithmetic is the contract of include/os2r_box.h.  Every class test of a value (finite, NaN) is made on its bits
+// (os2r_bits.hpp): the library is built without NaN and infinity semantics.
 //
-// The kernel below is still a copy of os2r_ilqr.hpp's text, against the rule of DESIGN.md section 4: as one function template
-// with a compile-time switch, the plain fp64 kernel measured 0.3 to 0.7 % slower at mu != 0 in both forms of the template
-// that were timed (profiles/refactor_bodies_ab.txt).  os2r_ilqr_box.hpp holds a third text, this kernel with the box QP in phase 2a
-// (profiles/ilqr_box_isa.txt has why it is no switch of this one).  Whoever changes one of the three texts changes the others.
+// This is the third text of the backward pass, next to os2r_ilqr.hpp and os2r_ilqr_mu.hpp, against the rule of DESIGN.md
+// section 4.  Whoever changes one of the three texts changes the others.
 #pragma once
 #include "os2r_ilqr.hpp"
-#include "os2r_bits.hpp"   // steer_invalid
-#include "../../include/os2r_steer.h"
+#include "os2r_bits.hpp"   // steer_invalid, steer_finite, steer_nan
+#include "../../include/os2r_box.h"
 
 namespace os2r {
 
 template <typename T>
-struct IlqrMuArgs {
-  IlqrArgs<T> base;                // as os2rc_ilqr_backward fills it; base.mu is not read
-  const T* __restrict__ mu;        // [M]
+struct IlqrBoxArgs {
+  IlqrArgs<T> base;                // as os2rc_ilqr_backward fills it; base.actions is always set; base.mu is read where mu is null
+  const T* __restrict__ mu;        // [M] or null
+  uint8_t* __restrict__ clamp;     // [K][M] or null
+  T lo[2], hi[2];                  // rounded to T by the host; -inf / +inf: no bound
 };
 
 template <typename T, int NQ>
-__global__ __launch_bounds__(kLqrEnvs * (2 * NQ + 2)) void ilqr_backward_mu_kernel(const IlqrMuArgs<T> PM) {
+__global__ __launch_bounds__(kLqrEnvs * (2 * NQ + 2)) void ilqr_backward_box_kernel(const IlqrBoxArgs<T> PM) {
 #pragma clang fp contract(off)
   constexpr int n = 2 * NQ, E = kLqrEnvs;
   const IlqrArgs<T>& P = PM.base;
@@ -49,14 +51,17 @@ __global__ __launch_bounds__(kLqrEnvs * (2 * NQ + 2)) void ilqr_backward_mu_kern
   const long long stride = (col_lane ? n : 2) * L;
   const T* gbase = col_lane ? P.lx : P.lu;
   const T* grad = gbase ? gbase + (long long)(col_lane ? c : c - n) * L + m : nullptr;
-  // the trajectory's mu, once: negative or not finite runs as 0 with every knot refused
-  const T mu_in = PM.mu[m];
-  const bool mu_bad = steer_invalid(mu_in);
+  // the trajectory's mu, once: negative or not finite runs as 0 with every knot refused (the host has checked the scalar)
+  const T mu_in = PM.mu ? PM.mu[m] : P.mu;
+  const bool mu_bad = PM.mu != nullptr && steer_invalid(mu_in);
   const T mu = mu_bad ? T(0) : mu_in;
   const bool reg = mu != T(0);
+  // the box: which of its four sides there are
+  const T lo0 = PM.lo[0], lo1 = PM.lo[1], hi0 = PM.hi[0], hi1 = PM.hi[1];
+  const bool has_lo0 = steer_finite(lo0), has_lo1 = steer_finite(lo1), has_hi0 = steer_finite(hi0), has_hi1 = steer_finite(hi1);
 
   {  // Q and the step sizes for everybody (read with a lane index: from the argument segment as memory, not from a copy of the struct)
-    const OS2R_CONST IlqrMuArgs<T>* ka = (const OS2R_CONST IlqrMuArgs<T>*)__builtin_amdgcn_kernarg_segment_ptr();
+    const OS2R_CONST IlqrBoxArgs<T>* ka = (const OS2R_CONST IlqrBoxArgs<T>*)__builtin_amdgcn_kernarg_segment_ptr();
     if ((int)threadIdx.x < n * n) sQ[threadIdx.x] = ka->base.q[threadIdx.x];
     if ((int)threadIdx.x < OS2RC_MAX_ALPHAS) sAl[threadIdx.x] = ka->base.alpha[threadIdx.x];
   }
@@ -77,6 +82,13 @@ __global__ __launch_bounds__(kLqrEnvs * (2 * NQ + 2)) void ilqr_backward_mu_kern
 #pragma unroll
   for (int l = 0; l < n; ++l) vn[l] = v[l] = src[l * stride + (long long)k * M];
   T gr = grad ? grad[(long long)k * M] : T(0), grn = gr;
+  // the knot's nominal actions, for the column lanes
+  T na0 = T(0), na1 = T(0);
+  if (col_lane) {
+    na0 = P.actions[2 * ((long long)k * M + m) + 0];
+    na1 = P.actions[2 * ((long long)k * M + m) + 1];
+  }
+  T nn0 = na0, nn1 = na1;
 
   for (; k >= 0; --k) {
     if (!col_lane) {
@@ -84,11 +96,15 @@ __global__ __launch_bounds__(kLqrEnvs * (2 * NQ + 2)) void ilqr_backward_mu_kern
       for (int l = 0; l < n; ++l) sB[(l * 2 + (c - n)) * E + e] = v[l];
     }
     __syncthreads();
-    // the next knot's column and gradient entry, in flight during this knot
+    // the next knot's column, gradient entry and nominal actions, in flight during this knot
     if (k > 0) {
 #pragma unroll
       for (int l = 0; l < n; ++l) vn[l] = src[l * stride + (long long)(k - 1) * M];
       if (grad) grn = grad[(long long)(k - 1) * M];
+      if (col_lane) {
+        nn0 = P.actions[2 * ((long long)(k - 1) * M + m) + 0];
+        nn1 = P.actions[2 * ((long long)(k - 1) * M + m) + 1];
+      }
     }
     // phase 1
     T pv[n];
@@ -135,17 +151,64 @@ __global__ __launch_bounds__(kLqrEnvs * (2 * NQ + 2)) void ilqr_backward_mu_kern
       k1 = (t00 * g1 - s01 * g0) / det;
       f0 = lqr_neg((t11 * qu0 - s01 * qu1) / det);
       f1 = lqr_neg((t00 * qu1 - s01 * qu0) / det);
-      k0 = ok ? k0 : T(0);
-      k1 = ok ? k1 : T(0);
-      f0 = ok ? f0 : T(0);
-      f1 = ok ? f1 : T(0);
+      // B1: the box around the clamped nominal
+      const T a00 = na0 < T(-1) ? T(-1) : (na0 > T(1) ? T(1) : na0);
+      const T a01 = na1 < T(-1) ? T(-1) : (na1 > T(1) ? T(1) : na1);
+      const T dlo0 = lo0 - a00, dhi0 = hi0 - a00, dlo1 = lo1 - a01, dhi1 = hi1 - a01;
+      // B2
+      const bool inside = !steer_nan(f0) && !steer_nan(f1) && dlo0 <= f0 && f0 <= dhi0 && dlo1 <= f1 && f1 <= dhi1;
+      bool have = false;
+      unsigned cl = 0u;
+      // B3, B4: skipped where no trajectory of the wave leaves the box (a uniform branch)
+      if (__builtin_amdgcn_ballot_w64(ok && !inside) != 0ull) {
+        T best = T(0), w0 = T(0), w1 = T(0), wk0 = T(0), wk1 = T(0);
+        // the free row of K, should the other component be the clamped one
+        const T row0 = g0 / t00, row1 = g1 / t11;
+        // one candidate: component cc at b, the other at the clipped minimum along the edge
+        auto edge = [&](const bool there, const int cc, const bool upper, const T b) {
+          const T qj = cc == 0 ? qu1 : qu0, tjj = cc == 0 ? t11 : t00;
+          const T dloj = cc == 0 ? dlo1 : dlo0, dhij = cc == 0 ? dhi1 : dhi0;
+          const T raw = lqr_neg((qj + s01 * b) / tjj);
+          const bool below = raw < dloj, above = raw > dhij, pinned = below || above;
+          T u = below ? dloj : raw;
+          u = above ? dhij : u;
+          const T c0 = cc == 0 ? b : u, c1 = cc == 0 ? u : b;
+          const T val = T(0.5) * (((t00 * c0) * c0 + (t11 * c1) * c1) + T(2) * ((s01 * c0) * c1)) + (qu0 * c0 + qu1 * c1);
+          const bool alive = there && !steer_nan(raw) && steer_finite(val);
+          const bool take = alive && (!have || val < best);
+          const unsigned byte = (1u << cc) | (pinned ? 1u << (1 - cc) : 0u) | (upper ? 4u << cc : 0u) | (above ? 4u << (1 - cc) : 0u);
+          const T free_row = pinned ? T(0) : (cc == 0 ? row1 : row0);
+          best = take ? val : best;
+          w0 = take ? c0 : w0;
+          w1 = take ? c1 : w1;
+          wk0 = take ? (cc == 0 ? T(0) : free_row) : wk0;
+          wk1 = take ? (cc == 0 ? free_row : T(0)) : wk1;
+          cl = take ? byte : cl;
+          have = have || take;
+        };
+        edge(has_lo0, 0, false, dlo0);
+        edge(has_hi0, 0, true, dhi0);
+        edge(has_lo1, 1, false, dlo1);
+        edge(has_hi1, 1, true, dhi1);
+        k0 = inside ? k0 : wk0;
+        k1 = inside ? k1 : wk1;
+        f0 = inside ? f0 : w0;
+        f1 = inside ? f1 : w1;
+      }
+      const bool solved = ok && (inside || have);
+      cl = (ok && !inside && have) ? cl : 0u;
+      k0 = solved ? k0 : T(0);
+      k1 = solved ? k1 : T(0);
+      f0 = solved ? f0 : T(0);
+      f1 = solved ? f1 : T(0);
       if (valid) {
         if (P.gain) {
           P.gain[(((long long)k * 2 + 0) * n + c) * M + m] = k0;
           P.gain[(((long long)k * 2 + 1) * n + c) * M + m] = k1;
         }
         if (c == 0) {
-          if (P.flag) P.flag[(long long)k * M + m] = ok ? 0 : 1;
+          if (P.flag) P.flag[(long long)k * M + m] = solved ? 0 : 1;
+          if (PM.clamp) PM.clamp[(long long)k * M + m] = (uint8_t)cl;
           if (P.ff) {
             P.ff[((long long)k * 2 + 0) * M + m] = f0;
             P.ff[((long long)k * 2 + 1) * M + m] = f1;
@@ -212,6 +275,8 @@ __global__ __launch_bounds__(kLqrEnvs * (2 * NQ + 2)) void ilqr_backward_mu_kern
 #pragma unroll
     for (int l = 0; l < n; ++l) v[l] = vn[l];
     gr = grn;
+    na0 = nn0;
+    na1 = nn1;
   }
 
   if (P.pmat_out || P.pvec_out) {
@@ -226,8 +291,8 @@ __global__ __launch_bounds__(kLqrEnvs * (2 * NQ + 2)) void ilqr_backward_mu_kern
   }
 }
 
-// the launch (os2r_ilqr_mu_inst.hip, once per dtype): 1 if there is no kernel for this nq
+// the launch (os2r_ilqr_box_inst.hip, once per dtype): 1 if there is no kernel for this nq
 template <typename T>
-int launch_ilqr_backward_mu(int nq, const IlqrMuArgs<T>& args, hipStream_t stream);
+int launch_ilqr_backward_box(int nq, const IlqrBoxArgs<T>& args, hipStream_t stream);
 
 }  // namespace os2r
