@@ -368,6 +368,7 @@ __device__ __forceinline__ float sqrt_t(float x) { return sqrtf(x); }
 // Cody-Waite form (exact product k*C1, FMA rounding relative to the small remainder) with the
 // library routine as the wave-uniform fallback beyond 2^19*pi/2; the kernels are the classical
 // minimax polynomials on [-pi/4, pi/4] (fdlibm k_sin / k_cos coefficients), ~1 ulp.
+// Absolute error <= 1 eps; the relative error is unbounded near multiples of pi/2, see tests/test_math_probe_host.py.
 __device__ __forceinline__ bool sincos_in_range(double x) { return fabs(x) < 8.2e5; }
 __device__ __forceinline__ bool sincos_in_range(float x) { return fabsf(x) < 200.0f; }   // beyond: library routine
 __device__ __forceinline__ void sincos_lib(double x, double& s, double& c) { sincos(x, &s, &c); }
@@ -482,16 +483,34 @@ __device__ __forceinline__ float fma_t(float a, float b, float c) { return __bui
 __device__ __forceinline__ double fabs_t(double x) { return fabs(x); }
 __device__ __forceinline__ float fabs_t(float x) { return fabsf(x); }
 
-// Finite test on the bit pattern of an *opaque* copy.  Under the no-NaN / no-Inf flags the optimiser
-// treats a NaN result as poison and may fold any test of it, bit tests included; the empty asm hides
-// where the value came from, so the exponent field is really inspected.
-__device__ __forceinline__ bool finite_t(double x) {
-  asm volatile("" : "+v"(x));
-  return ((__double_as_longlong(x) >> 52) & 0x7ff) != 0x7ff;
+// Finite test on the bit pattern, with the exponent MASK as the opaque part: it passes through an empty asm in a scalar
+// register, so the compiler sees a word and-ed and compared with a value it does not know, and compiles the test as written.
+// Under the no-NaN / no-Inf flags the optimiser treats a NaN result as poison and may fold any test of it, bit tests included.
+// Hiding the floating-point value alone (this function's earlier form: the asm on x itself) is not enough: the mask-and-compare
+// with the exponent's own constant on the bits of a float that came out of an asm is recognised as a class test of that float
+// and folded to true (os2r_bits.hpp has the same finding; tests/test_gpu_math_probe.py holds every class test against its bit
+// patterns).  An opaque copy of every tested value instead costs a register each: the fp32 counting kernel of fixed_hip spilled.
+__device__ __forceinline__ unsigned exponent_mask(double) { unsigned k = 0x7ff00000u; asm("" : "+s"(k)); return k; }
+__device__ __forceinline__ unsigned exponent_mask(float) { unsigned k = 0x7f800000u; asm("" : "+s"(k)); return k; }
+// (k: exponent_mask of the type, fetched once where many values are tested)
+__device__ __forceinline__ bool finite_t(double x, unsigned k) { return ((unsigned)__double2hiint(x) & k) != k; }
+__device__ __forceinline__ bool finite_t(float x, unsigned k) { return ((unsigned)__float_as_int(x) & k) != k; }
+__device__ __forceinline__ bool finite_t(double x) { return finite_t(x, exponent_mask(x)); }
+__device__ __forceinline__ bool finite_t(float x) { return finite_t(x, exponent_mask(x)); }
+
+// Not finite, or beyond 1e30 in magnitude (the step kernels' guard on q and qd): ONE integer comparison of the magnitude bits,
+// which order as the values do, with the infinities and the NaNs above every finite value.  For finite x this is fabs(x) > 1e30
+// exactly.  The mask is the opaque part, so the compiler does not see a fabs and a floating-point comparison in it.
+__device__ __forceinline__ bool wild_t(float x) {
+  unsigned m = 0x7fffffffu;
+  asm("" : "+s"(m));
+  return ((unsigned)__float_as_int(x) & m) > (unsigned)__float_as_int(1e30f);
 }
-__device__ __forceinline__ bool finite_t(float x) {
-  asm volatile("" : "+v"(x));
-  return ((__float_as_int(x) >> 23) & 0xff) != 0xff;
+__device__ __forceinline__ bool wild_t(double x) {
+  unsigned m = 0x7fffffffu;
+  asm("" : "+s"(m));
+  const unsigned long long b = ((unsigned long long)((unsigned)__double2hiint(x) & m) << 32) | (unsigned)__double2loint(x);
+  return b > (unsigned long long)__double_as_longlong(1e30);
 }
 
 // symmetric 3x3 stored as xx xy xz yy yz zz

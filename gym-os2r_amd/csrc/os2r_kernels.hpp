@@ -33,7 +33,9 @@ __device__ __forceinline__ double tanh_t(double x) {
     r = __builtin_fma(x, z * p, x);
   }
   if (__ballot(!small) != 0ull) {
-    const double t = exp(2.0 * ax);                 // inf for |x| > 354: the quotient is 0, the result 1
+    // (the argument is capped where the result is 1 already: 2 |x| itself overflows in the last binade, and exp of an infinity is
+    // a NaN under the no-infinity flags -- tanh_t(DBL_MAX) was a NaN; every finite result is what it was)
+    const double t = exp(2.0 * __builtin_fmin(ax, 354.0));    // exp(708) = 3e307: the quotient is 7e-308, the result 1
     const double big = __builtin_copysign(1.0 - 2.0 / (t + 1.0), x);
     r = small ? r : big;
   }
@@ -91,6 +93,7 @@ __device__ __forceinline__ void observe(TaskPtr<T> ts, const T (&q)[NQ], const T
                                         T h1a, T h1b, T (&obs)[OS2R_MAX_OBS], bool& done, unsigned& reason) {
 #pragma clang fp contract(off)
   done = false;
+  const unsigned fmask = exponent_mask(T(0));   // one opaque mask for the finite tests of all slots
   reason = 0u;   // bit d: observation slot d is outside the reset space (or not finite): which one ended the episode
   int D = LAY::kStatic ? LAY::kDim : ts->obs_dim;
   if constexpr (!LAY::kStatic) asm volatile("" : "+s"(D));   // one copy in a register: not re-fetched (and waited for) slot after slot
@@ -138,7 +141,7 @@ __device__ __forceinline__ void observe(TaskPtr<T> ts, const T (&q)[NQ], const T
       if (kind == OS2R_OBS_POS_PERIODIC_NORM || kind == OS2R_OBS_POS_PERIODIC_RAW) x = wrap_pi(x);
       // done: the reference tests the observation against reset_space; done_lo/done_hi are the
       // exact pre-images of that test on x (host-side bisection), NaN counts as done
-      if (x < dlo_[k] || x > dhi_[k] || !finite_t(x)) { done = true; reason |= 1u << d; }   // NaN counts as done
+      if (x < dlo_[k] || x > dhi_[k] || !finite_t(x, fmask)) { done = true; reason |= 1u << d; }   // NaN counts as done
       T o = x;
       if (kind == OS2R_OBS_POS_NORM || kind == OS2R_OBS_POS_PERIODIC_NORM || kind == OS2R_OBS_TORQUE_NORM) {
         const T lo = lo_[k], hi = hi_[k];
@@ -828,7 +831,7 @@ __device__ __forceinline__ void step_body(const StepArgs<T>& A) {
 
     bool bad = false;
 #pragma unroll
-    for (int i = 0; i < NQ; ++i) bad = bad || !finite_t(q[i]) || !finite_t(qd[i]) || fabs_t(q[i]) > T(1e30) || fabs_t(qd[i]) > T(1e30);
+    for (int i = 0; i < NQ; ++i) bad = bad || wild_t(q[i]) || wild_t(qd[i]);     // not finite, or beyond 1e30
 
     // (the bookkeeping of an environment -- action history, step and episode counters -- is fetched where it is used and
     // stored at the end of every env-step, in a rollout as well: nothing of it is held across the physics iterations)
