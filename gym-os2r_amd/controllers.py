@@ -16,7 +16,7 @@ import math
 
 import torch
 
-from . import abi, box as box_lib, cem, control, critic, ekf, es, mppi, norm, npg, pf, pg, ppo, search, steer, ukf
+from . import abi, box as box_lib, cem, cma, control, critic, ekf, es, mppi, norm, npg, pf, pg, ppo, search, steer, ukf
 from ._lib import Os2rError, _ptr
 
 NOMINAL_KEYS = ("cost", "actions", "obs", "end_obs", "lx", "lu", "p_final")
@@ -1502,6 +1502,175 @@ class Controllers:
         self.es_update_into(returns, theta, theta_new, sigma_r, count, used, kept, directions=S, generation=generation, step_size=step_size,
                             top=top, sigma_floor=sigma_floor, seed=seed, pop_offset=pop_offset, grad=grad, score=score)
         return theta_new, sigma_r, count, used, grad, kept if want_kept else None
+
+    # -- CMA-ES: factors and correlated samples, and the update of mean, step size, covariance and paths ------
+    def _cma_state(self, what, state, name="state"):
+        """state = (mean [M, 2, D+1], sigma [M], cov [M, E, E], p_sigma [M, E], p_c [M, E]) -> (its five tensors, M), the shapes
+        checked against the mean's."""
+        E = 2 * (self.D + 1)
+        if not isinstance(state, (tuple, list)) or len(state) != 5 or not isinstance(state[0], torch.Tensor) or state[0].dim() != 3 \
+                or state[0].shape[0] < 1:
+            raise ValueError(f"{what}: {name} must be (mean [M, 2, {self.D + 1}], sigma [M], cov [M, {E}, {E}], p_sigma [M, {E}], "
+                             f"p_c [M, {E}]) with M >= 1, got {type(state)}")
+        M = int(state[0].shape[0])
+        shapes = ((M, 2, self.D + 1), (M,), (M, E, E), (M, E), (M, E))
+        rows = tuple((t, shape, None, f"{name}: {n}") for t, shape, n in zip(state, shapes, ("mean", "sigma", "cov", "p_sigma", "p_c")))
+        if any(t is None for t in state):
+            raise ValueError(f"{what}: {name}: mean, sigma, cov, p_sigma and p_c are all required")
+        self._outs(what, rows)
+        return rows, M
+
+    def _cma_shape(self, what, M, samples, generation, seed, pop_offset):
+        """The integers both calls share -> (S, N = S M, seed, pop_offset, generation)."""
+        S = _count(what, "samples", samples)
+        if S < 2 or S > cma.MAX_SAMPLES:
+            raise ValueError(f"{what}: samples must be in 2..2^27 - 1, got {S}")
+        if S * M > 2 ** 31 - 1:
+            raise ValueError(f"{what}: samples x populations = {S * M} exceeds 2^31 - 1")
+        words = []
+        for name, v in (("generation", generation), ("pop_offset", pop_offset)):
+            if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v < 2 ** 32:
+                raise ValueError(f"{what}: {name} must be an integer in 0..2^32 - 1, got {v!r}")
+            words.append(v)
+        if seed is not None and (isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 64):
+            raise ValueError(f"{what}: seed must be None (the handle's) or an integer in 0..2^64 - 1, got {seed!r}")
+        return S, S * M, seed, words[1], words[0]
+
+    def cma_init(self, theta, sigma0):
+        """The CMA-ES state of M populations that start at theta [M, 2, D+1] with the step size sigma0 (a float > 0, or a tensor
+        [M]): -> (mean, sigma [M], cov [M, E, E] = I, p_sigma [M, E] = 0, p_c [M, E] = 0), new tensors in the handle's dtype."""
+        what = "cma_init"
+        if not isinstance(theta, torch.Tensor) or theta.dim() != 3 or theta.shape[0] < 1 or tuple(theta.shape[1:]) != (2, self.D + 1):
+            raise ValueError(f"{what}: theta must be a tensor [M, 2, {self.D + 1}] with M >= 1, got {tuple(getattr(theta, 'shape', ()))}")
+        M, E = int(theta.shape[0]), 2 * (self.D + 1)
+        if isinstance(sigma0, torch.Tensor):
+            sigma = self._in(sigma0, (M,)).clone()
+        else:
+            sigma = torch.full((M,), _finite(what, "sigma0", math.nan if isinstance(sigma0, bool) else sigma0, _invertible, "> 0", repr(sigma0)),
+                               dtype=self.dtype, device=self.device)
+        cov = torch.eye(E, dtype=self.dtype, device=self.device).repeat(M, 1, 1)
+        zero = lambda: torch.zeros(M, E, dtype=self.dtype, device=self.device)
+        return self._in(theta, (M, 2, self.D + 1)).clone(), sigma, cov, zero(), zero()
+
+    def cma_sample_into(self, state, factor, failed, weights, *, samples: int, generation: int, seed=None, pop_offset: int = 0, z=None):
+        """Allocation-free factors and samples of one CMA-ES generation of M populations, S = samples each (include/os2r_cma.h:
+        os2rk_cma_sample; the arithmetic is spelled out there).  Of state = (mean [M, 2, D+1], sigma [M], cov [M, E, E], p_sigma,
+        p_c) mean, sigma and the lower triangle of cov are read; factor [M, E, E], failed [M] int32, weights [N, 2, D+1] with
+        N = S M lanes and z [N, 2, D+1] (or None) are written: lane s M + m is mean_m + sigma_m A_m z[m, s], what rollout_policy
+        takes as per-environment weights, or mean_m where the factor of C_m failed (failed[m] = the column + 1) or sigma_m is
+        not finite and positive (failed[m] = E + 1).  The normals are a pure function of (seed, pop_offset + m, s, generation)
+        under the stepper's counter RNG (stream 7); seed None is the handle's seed.  Shapes, dtypes, device, contiguity,
+        alignment and overlap are checked before the library is called (it takes addresses)."""
+        what = "cma_sample"
+        rows, M = self._cma_state(what, state)
+        S, N, seed, off, gen = self._cma_shape(what, M, samples, generation, seed, pop_offset)
+        if any(t is None for t in (factor, failed, weights)):
+            raise ValueError(f"{what}: factor, failed and weights are required")
+        D, E = self.D, 2 * (self.D + 1)
+        inputs = rows[:3]
+        outputs = ((factor, (M, E, E), None, "factor"), (failed, (M,), torch.int32, "failed"), (weights, (N, 2, D + 1), None, "weights"),
+                   (z, (N, 2, D + 1), None, "z"))
+        self._outs(what, outputs)
+        self._es_aligned(what, ((state[0], "state: mean"), (weights, "weights"), (z, "z")))
+        self._no_overlap(what, inputs, outputs)
+        _call(cma, "os2rk_cma_sample", "os2rk_last_error", C.byref(self._layout()), M, S, 0, int(self.cfg.seed) if seed is None else seed, off,
+              gen, _ptr(state[0]), _ptr(state[1]), _ptr(state[2]), _ptr(factor), _ptr(failed), _ptr(weights), _ptr(z), self._stream())
+
+    def cma_sample(self, state, samples: int, generation: int, seed=None, pop_offset: int = 0, want_z: bool = False):
+        """The S M sampled policies of one CMA-ES generation, in two launches (include/os2r_cma.h: os2rk_cma_sample): state is
+        what cma_init or cma_update returned, S = samples.
+        -> (weights [N, 2, D+1], N = S M: lane s M + m is sample s of population m -- rollout_policy(K, weights,
+        first_episode=True) on a handle of N environments returns what cma_update takes, and copy_envs_from(real,
+        arange(N) % M) lines the environments up without a gather; factor [M, E, E]: the lower Cholesky factor of every
+        covariance, which cma_update reads; failed [M] int32: 0, or why population m was not sampled; z [N, 2, D+1] | None: the
+        normals, row s M + m, for tests -- cma_update regenerates them)."""
+        what = "cma_sample"
+        _, M = self._cma_state(what, state)
+        S, N, _, _, _ = self._cma_shape(what, M, samples, generation, seed, pop_offset)      # (here too: they size what is allocated)
+        E = 2 * (self.D + 1)
+        weights, factor, failed = self._new(N, 2, self.D + 1), self._new(M, E, E), self._new(M, dtype=torch.int32)
+        z = self._new(N, 2, self.D + 1) if want_z else None
+        self.cma_sample_into(state, factor, failed, weights, samples=S, generation=generation, seed=seed, pop_offset=pop_offset, z=z)
+        return weights, factor, failed, z
+
+    def cma_update_into(self, returns, state, factor, failed, state_new, count, status, rank, *, samples: int, generation: int, rankw,
+                        constants, seed=None, pop_offset: int = 0, yw=None, ps_norm=None, growth=None):
+        """Allocation-free CMA-ES update of M populations from the returns of their S lanes, larger is better
+        (include/os2r_cma.h: os2rk_cma_update; the arithmetic and its order are spelled out there).  returns [N] (N = S M, the
+        lanes of cma_sample), state, factor [M, E, E] and failed [M] int32 (as cma_sample wrote them) and rankw [mu] (the
+        recombination weights, in the handle's dtype on its device) are read; constants is a cma.Os2rkCmaConstants
+        (cma.constants() has Hansen's defaults).  state_new (five tensors as state), count [M] int32, status [M] int32 and rank
+        [N] int32 (all required: rank is the scratch the sums read) and yw [M, 2, D+1], ps_norm [M], growth [M] (each or None)
+        are written.  generation, seed and pop_offset are those of the cma_sample call whose weights were rolled out.  An output
+        may not overlap an input or another output: the caller swaps two states.  Shapes, dtypes, device, contiguity,
+        alignment and overlap are checked before the library is called (it takes addresses)."""
+        what = "cma_update"
+        rows, M = self._cma_state(what, state)
+        S, N, seed, off, gen = self._cma_shape(what, M, samples, generation, seed, pop_offset)
+        if not isinstance(rankw, torch.Tensor) or rankw.dim() != 1 or not 1 <= rankw.shape[0] <= S:
+            raise ValueError(f"{what}: rankw must be a tensor [mu] with 1 <= mu <= samples = {S}, got {tuple(getattr(rankw, 'shape', ()))}")
+        mu = int(rankw.shape[0])
+        if not isinstance(constants, cma.Os2rkCmaConstants):
+            raise ValueError(f"{what}: constants must be a cma.Os2rkCmaConstants (cma.constants() makes one), got {type(constants)}")
+        for name in cma.CONSTANT_NAMES:
+            if not math.isfinite(getattr(constants, name)):
+                raise ValueError(f"{what}: constants.{name} must be finite, got {getattr(constants, name)}")
+        if any(t is None for t in (returns, factor, failed, count, status, rank)):
+            raise ValueError(f"{what}: returns, factor, failed, count, status and rank are required")
+        out_rows, M_new = self._cma_state(what, state_new, "state_new")
+        if M_new != M:
+            raise ValueError(f"{what}: state_new holds {M_new} populations, state {M}")
+        D, E, i32 = self.D, 2 * (self.D + 1), torch.int32
+        inputs = ((returns, (N,), None, "returns"), (rankw, (mu,), None, "rankw")) + rows + \
+                 ((factor, (M, E, E), None, "factor"), (failed, (M,), i32, "failed"))
+        outputs = out_rows + ((count, (M,), i32, "count"), (status, (M,), i32, "status"), (rank, (N,), i32, "rank"),
+                              (yw, (M, 2, D + 1), None, "yw"), (ps_norm, (M,), None, "ps_norm"), (growth, (M,), None, "growth"))
+        self._outs(what, inputs + outputs)
+        self._es_aligned(what, ((state[0], "state: mean"), (state_new[0], "state_new: mean"), (yw, "yw")))
+        self._no_overlap(what, inputs, outputs)
+        _call(cma, "os2rk_cma_update", "os2rk_last_error", C.byref(self._layout()), M, S, mu, 0, int(self.cfg.seed) if seed is None else seed,
+              off, gen, _ptr(returns), _ptr(rankw), *[_ptr(t) for t in state], _ptr(factor), _ptr(failed), C.byref(constants),
+              *[_ptr(t) for t in state_new], _ptr(count), _ptr(status), _ptr(rank), _ptr(yw), _ptr(ps_norm), _ptr(growth), self._stream())
+
+    def cma_update(self, returns, state, factor, failed, samples: int, generation: int, parents=None, age=None, sigma_min: float = 1e-8,
+                   sigma_max: float = 1.0, seed=None, pop_offset: int = 0, want_yw: bool = False, want_norm: bool = False,
+                   want_growth: bool = False):
+        """The update of Cholesky-CMA-ES (Hansen and Ostermeier 2001; Suttorp, Hansen and Igel 2009) of M populations in one call
+        (include/os2r_cma.h: os2rk_cma_update), with Hansen's default constants (cma.constants): returns [N] is what
+        rollout_policy(K, weights, first_episode=True) returned for the weights of cma_sample(state, samples, generation, ...),
+        as it lies on the device; factor and failed are that call's, and so are generation, seed and pop_offset.  Per
+        population: a lane is valid where its return is finite; the mu = parents (None: S // 2) valid lanes of the largest
+        return are the parents (equal returns: the lower s first), weighted by rank; the mean moves by sigma times their weighted
+        step, the step-size path by their weighted normals -- regenerated from the counter RNG, not read --, the covariance by
+        the rank-one term of its path and the rank-mu term of the parents' steps, and sigma by the length of its path.  age is the
+        number of updates the state has seen (None: generation); it enters the stall test of the path only.  A population
+        whose factor failed (status 2) or that has fewer than mu valid lanes (status 1) keeps its state.
+        -> (state_new: five new tensors as state; count [M] int32: the valid lanes; status [M] int32; rank [N] int32: the rank
+        of every lane among those of its population; yw [M, 2, D+1] | None: the weighted step; ps_norm [M] | None: the length of
+        the new step-size path; growth [M] | None: the factor on sigma before its clamp to [sigma_min, sigma_max])."""
+        what = "cma_update"
+        _, M = self._cma_state(what, state)
+        S, N, _, _, gen = self._cma_shape(what, M, samples, generation, seed, pop_offset)      # (here too: they size what is allocated)
+        if parents is not None and (isinstance(parents, bool) or not isinstance(parents, int) or not 1 <= parents <= S):
+            raise ValueError(f"{what}: parents must be None (samples // 2) or an integer in 1..{S}, got {parents!r}")
+        if age is not None and (isinstance(age, bool) or not isinstance(age, int) or age < 0):
+            raise ValueError(f"{what}: age must be None (the generation) or an integer >= 0, got {age!r}")
+        lo = _finite(what, "sigma_min", math.nan if isinstance(sigma_min, bool) else sigma_min, _not_negative, ">= 0", repr(sigma_min))
+        hi = _finite(what, "sigma_max", math.nan if isinstance(sigma_max, bool) else sigma_max, lambda x: x >= lo, ">= sigma_min", repr(sigma_max))
+        D, E, i32 = self.D, 2 * (self.D + 1), torch.int32
+        rankw, constants = cma.constants(E, S, parents, gen if age is None else age, lo, hi)
+        made = self.__dict__.setdefault("_cma_rankw", {})
+        if (S, len(rankw)) not in made:                                                      # the weights on the device, once per shape
+            made[(S, len(rankw))] = torch.tensor(rankw, dtype=torch.float64).to(self.dtype).to(self.device)
+        state_new = (self._new(M, 2, D + 1), self._new(M), self._new(M, E, E), self._new(M, E), self._new(M, E))
+        count, status, rank = self._new(M, dtype=i32), self._new(M, dtype=i32), self._new(N, dtype=i32)
+        yw = self._new(M, 2, D + 1) if want_yw else None
+        ps_norm = self._new(M) if want_norm else None
+        growth = self._new(M) if want_growth else None
+        self.cma_update_into(returns, state, factor, failed, state_new, count, status, rank, samples=S, generation=generation,
+                             rankw=made[(S, len(rankw))], constants=constants, seed=seed, pop_offset=pop_offset, yw=yw, ps_norm=ps_norm,
+                             growth=growth)
+        return state_new, count, status, rank, yw, ps_norm, growth
 
     # -- running observation whitening: the statistics, the fold and the gradient back ---------
     def _norm_state(self, what, state, P=None, required=True):

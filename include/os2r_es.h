@@ -15,7 +15,7 @@
  *
  * Out of scope: MLP policies and scheduled policies, one-sided (non-antithetic) sampling, centred-rank or other fitness
  * shaping, the observation normalisation of ARS V2 (since built as `libos2r_norm.so`), a nu, step_size or top per population,
- * covariance adaptation (CMA-ES),
+ * covariance adaptation (CMA-ES) (since built as `libos2r_cma.so`),
  * weight decay and the optimiser itself (grad_dev is there for the caller's own), a shared noise table, and updating theta in
  * place: an output may not overlap an input, so the caller swaps two buffers.
  */
