@@ -1,7 +1,7 @@
 """The controller calls of a HipSim: LQR gains, the iLQR backward pass (plain, with a mu per trajectory, or under box limits on the
 actions), its line search with and without a steered mu, the MPPI
 update, the cross-entropy update, the particle-filter update, the Kalman filter update, the two calls of the unscented Kalman filter (its sigma points and its update), the
-score-function policy gradient, the two calls of the critic (GAE(lambda) and the linear value fit), the clipped-surrogate (PPO) gradient, the natural-gradient step, the two calls of evolution-strategy search (the perturbation and the ARS update) and the three of running observation whitening (the statistics, the fold and the gradient back), each as an allocation-free ``*_into`` on tensors in the kernel's layout and an allocating
+score-function policy gradient, the two calls of the critic (GAE(lambda) and the linear value fit), the clipped-surrogate (PPO) gradient, the natural-gradient step, the two calls of evolution-strategy search (the perturbation and the ARS update), the three of running observation whitening (the statistics, the fold and the gradient back) and the two of system identification (the parameter lanes and the Levenberg-Marquardt update), each as an allocation-free ``*_into`` on tensors in the kernel's layout and an allocating
 wrapper around it.  ``Controllers`` is the plain base class HipSim (gym_os2r_amd.sim) inherits them from; it uses the handle's
 ``_out``, ``_in``, ``_new``, ``_layout``, ``_stream`` and ``_check``.
 
@@ -16,7 +16,7 @@ import math
 
 import torch
 
-from . import abi, box as box_lib, cem, cma, control, critic, ekf, es, mppi, norm, npg, pf, pg, ppo, search, steer, ukf
+from . import abi, box as box_lib, cem, cma, control, critic, ekf, es, mppi, norm, npg, pf, pg, ppo, search, steer, sysid, ukf
 from ._lib import Os2rError, _ptr
 
 NOMINAL_KEYS = ("cost", "actions", "obs", "end_obs", "lx", "lu", "p_final")
@@ -1835,3 +1835,194 @@ class Controllers:
         out = torch.empty_like(source)
         self.norm_unfold_into(source, state, out, std_floor=std_floor, policy_fastest=fastest)
         return back(out)
+
+    # -- system identification: the parameter lanes, and the Gauss-Newton / Levenberg-Marquardt update -------
+    def _sysid_steps(self, what, sel, h, lo, hi):
+        """The identified parameters: sel, P pairs (field, index) or None (where the call does not read them), and the steps and
+        bounds h, lo, hi, P numbers each -> (P, sel as int32 [2 P] or None, h, lo, hi as double [P]), checked."""
+        def numbers(name, v):
+            try:
+                items = list(v.tolist() if hasattr(v, "tolist") else v)
+                out = [float(x) for x in items]
+            except (TypeError, ValueError):
+                raise ValueError(f"{what}: {name} must be a sequence of numbers, got {type(v)}") from None
+            if any(isinstance(x, bool) for x in items):
+                raise ValueError(f"{what}: {name} must be a sequence of numbers, got a bool")
+            return out
+
+        def rounded(x):
+            """x as the library rounds it: once, to the handle's dtype."""
+            return x if self.dtype == torch.float64 else float(torch.tensor(x, dtype=torch.float64).to(torch.float32))
+        h, lo, hi = numbers("h", h), numbers("lo", lo), numbers("hi", hi)
+        P = len(h)
+        if not 1 <= P <= sysid.MAX_PARAMS or len(lo) != P or len(hi) != P:
+            raise ValueError(f"{what}: h, lo and hi must hold one entry for each of 1..{sysid.MAX_PARAMS} parameters, got {P}, {len(lo)} and {len(hi)}")
+        for p in range(P):
+            if not math.isfinite(h[p]) or not h[p] > 0.0 or not math.isfinite(rounded(h[p])) or not rounded(h[p]) > 0.0:
+                raise ValueError(f"{what}: h[{p}] must be finite and > 0 in the handle's dtype, got {h[p]}")
+            if math.isnan(lo[p]) or math.isnan(hi[p]) or lo[p] > hi[p]:
+                raise ValueError(f"{what}: lo[{p}] <= hi[{p}] must hold (infinite bounds are allowed), got {lo[p]} and {hi[p]}")
+        pairs = None
+        if sel is not None:
+            try:
+                flat = [(f, i) for f, i in sel]
+            except (TypeError, ValueError):
+                raise ValueError(f"{what}: sel must be a sequence of (field, index) pairs, got {sel!r}") from None
+            if len(flat) != P:
+                raise ValueError(f"{what}: sel names {len(flat)} parameters, h holds {P}")
+            seen = set()
+            for f, i in flat:
+                if any(isinstance(x, bool) or not isinstance(x, int) for x in (f, i)) or f not in sysid.FIELDS \
+                        or not 0 <= i < (1 if f == abi.PARAM_GRAVITY else self.nq):
+                    raise ValueError(f"{what}: sel: ({f!r}, {i!r}) is no entry of a parameter field of a chain of {self.nq} dofs")
+                if (f, i) in seen:
+                    raise ValueError(f"{what}: sel names ({f}, {i}) twice")
+                seen.add((f, i))
+            pairs = (C.c_int32 * (2 * P))(*[x for pair in flat for x in pair])
+        dbl = C.c_double * P
+        return P, pairs, dbl(*h), dbl(*lo), dbl(*hi)
+
+    def _sysid_sets(self, what, theta, P):
+        """theta [T, P] -> T."""
+        if not isinstance(theta, torch.Tensor) or theta.dim() != 2 or not 1 <= theta.shape[0] <= sysid.MAX_SETS or theta.shape[1] != P:
+            raise ValueError(f"{what}: theta must be a tensor [T, {P}] with T in 1..2^26 - 1, got {tuple(getattr(theta, 'shape', ()))}")
+        return int(theta.shape[0])
+
+    def _sysid_state(self, what, state, T, P, name="state"):
+        """state = (theta_best [T, P], cost_best [T], hess [T, P, P], grad [T, P], lam [T], status [T] int32, iters [T] int32)
+        -> its rows as _outs takes them, checked."""
+        if not isinstance(state, (tuple, list)) or len(state) != 7 or any(t is None for t in state):
+            raise ValueError(f"{what}: {name} must be (theta_best [T, P], cost_best [T], hess [T, P, P], grad [T, P], lam [T], status [T] int32, "
+                             f"iters [T] int32), got {type(state)}")
+        shapes = ((T, P), (T,), (T, P, P), (T, P), (T,), (T,), (T,))
+        dtypes = (None,) * 5 + (torch.int32,) * 2
+        rows = tuple((t, shape, dtype, f"{name}: {n}") for t, shape, dtype, n in zip(state, shapes, dtypes, sysid.STATE))
+        self._outs(what, rows)
+        return rows
+
+    def sysid_init(self, theta0, lam0: float = 1e-3):
+        """The state of T parameter sets that start at theta0 [T, P] with the damping lam0 (a float > 0): -> (theta_best = theta0,
+        cost_best [T] = +inf, hess [T, P, P] = 0, grad [T, P] = 0, lam [T] = lam0, status [T] int32 = 0, iters [T] int32 = 0), new
+        tensors in the handle's dtype.  The first point sysid_perturb takes is theta0 itself."""
+        what = "sysid_init"
+        if not isinstance(theta0, torch.Tensor) or theta0.dim() != 2 or theta0.shape[0] < 1 or not 1 <= theta0.shape[1] <= sysid.MAX_PARAMS:
+            raise ValueError(f"{what}: theta0 must be a tensor [T, P] with T >= 1 and P in 1..{sysid.MAX_PARAMS}, got "
+                             f"{tuple(getattr(theta0, 'shape', ()))}")
+        T, P = int(theta0.shape[0]), int(theta0.shape[1])
+        lam = _finite(what, "lam0", math.nan if isinstance(lam0, bool) else lam0, _invertible, "> 0", repr(lam0))
+        new = lambda shape, value, dtype=None: torch.full(shape, value, dtype=dtype or self.dtype, device=self.device)
+        return (self._in(theta0, (T, P)).clone(), new((T,), math.inf), new((T, P, P), 0.0), new((T, P), 0.0), new((T,), lam),
+                new((T,), 0, torch.int32), new((T,), 0, torch.int32))
+
+    def sysid_perturb_into(self, theta, base, params, *, sel, h, lo, hi):
+        """Allocation-free parameter lanes of one identification step (include/os2r_sysid.h: os2ri_perturb; one launch).  theta
+        [T, P] (the point of every set) and base [4 nq + 1, M] (the packed parameters of the M segments, sysid.pack; segment m
+        belongs to set m mod T) are read; params [4 nq + 1, N], N = (2 P + 1) M, is written: lane s M + m gets base[:, m] with the
+        identified entries sel[p] = (field, index) at theta (s = 0 and every lane not their own), at min(theta + h, hi)
+        (s = 1 + p) or at max(theta - h, lo) (s = 1 + P + p).  sysid.field_view(params, nq, f) is what set_params(f, ...) takes,
+        without a copy.  Shapes, dtypes, device, contiguity and overlap are checked before the library is called."""
+        what = "sysid_perturb"
+        P, pairs, hs, los, his = self._sysid_steps(what, sel, h, lo, hi)
+        if sel is None:
+            raise ValueError(f"{what}: sel is required")
+        T = self._sysid_sets(what, theta, P)
+        F = sysid.rows(self.nq)
+        if not isinstance(base, torch.Tensor) or base.dim() != 2 or base.shape[1] < 1 or base.shape[1] % T:
+            raise ValueError(f"{what}: base must be a tensor [{F}, M] with M a multiple of the {T} sets, got {tuple(getattr(base, 'shape', ()))}")
+        M = int(base.shape[1])
+        if (2 * P + 1) * M > 2 ** 31 - 1 or F * (2 * P + 1) * M > 2 ** 32 - 1:
+            raise ValueError(f"{what}: (2 P + 1) M = {(2 * P + 1) * M} lanes exceed 2^31 - 1, or their {F} rows 2^32 - 1 entries")
+        if params is None:
+            raise ValueError(f"{what}: params is required")
+        inputs = ((theta, (T, P), None, "theta"), (base, (F, M), None, "base"))
+        outputs = ((params, (F, (2 * P + 1) * M), None, "params"),)
+        self._outs(what, inputs + outputs)
+        self._no_overlap(what, inputs, outputs)
+        _call(sysid, "os2ri_perturb", "os2ri_last_error", C.byref(self._layout()), P, T, M, pairs, hs, los, his, _ptr(theta), _ptr(base),
+              _ptr(params), self._stream())
+
+    def sysid_perturb(self, theta, base, *, sel, h, lo, hi):
+        """The parameter lanes of one identification step in one launch (include/os2r_sysid.h: os2ri_perturb): theta [T, P] is what
+        sysid_init started at or sysid_update returned as theta_next, base [4 nq + 1, M] the packed parameters of the segments.
+        -> params [4 nq + 1, (2 P + 1) M]; the loop goes on with set_params(f, sysid.field_view(params, nq, f)) for the five
+        fields, set_state, rollout(K, actions) and sysid_update."""
+        what = "sysid_perturb"
+        P, _, _, _, _ = self._sysid_steps(what, sel, h, lo, hi)
+        self._sysid_sets(what, theta, P)
+        if not isinstance(base, torch.Tensor) or base.dim() != 2 or base.shape[1] < 1 or (2 * P + 1) * base.shape[1] > 2 ** 31 - 1:
+            raise ValueError(f"{what}: base must be a tensor [{sysid.rows(self.nq)}, M], got {tuple(getattr(base, 'shape', ()))}")
+        params = self._new(sysid.rows(self.nq), (2 * P + 1) * int(base.shape[1]))
+        self.sysid_perturb_into(theta, base, params, sel=sel, h=h, lo=lo, hi=hi)
+        return params
+
+    def sysid_update_into(self, obs, meas, prec, theta, state, state_new, theta_next, sums, counts, *, h, lo, hi, constants, done=None,
+                          cost=None, valid=None, accepted=None, failed=None, delta=None):
+        """Allocation-free Levenberg-Marquardt update of T parameter sets from the rollout of their lanes (include/os2r_sysid.h:
+        os2ri_update; three stream-ordered launches, no host synchronisation; the arithmetic and its order are spelled out
+        there).  obs [K, N, D] (the rollout of the lanes of sysid_perturb), meas [K, M, D] (the logged observations; a reading
+        that is not finite is skipped), prec [D] (a slot whose weight is not finite and > 0 is dropped), theta [T, P] and h, lo,
+        hi (those of the sysid_perturb call that made the lanes), done [K, N] uint8 (or None) and state are read; constants is a
+        sysid.Os2riConstants (sysid.constants()).  state_new (seven tensors as state) and theta_next [T, P] (the point the next
+        sysid_perturb takes) are written, and cost [T], valid [T] int32, accepted [T] uint8, failed [T] int32 and delta [T, P]
+        (each or None); sums [E (M + T)] with E = P (P + 1) / 2 + P + 1 and counts [M + T] int32 are the call's scratch.  A segment
+        counts iff none of its lanes was done in the K steps and all its sums are finite.  A point is accepted iff it costs less
+        than the best so far; a rejected one raises lam by the factor grow, an accepted one lowers it; either way the next
+        point is the best one plus the damped Gauss-Newton step of the system stored with it, clamped to [lo, hi].  A set
+        whose status is not 0 (1: converged, 2: lam passed lam_max) passes through.  An output may not overlap an input or
+        another output: the caller swaps two states."""
+        what = "sysid_update"
+        P, _, hs, los, his = self._sysid_steps(what, None, h, lo, hi)
+        T = self._sysid_sets(what, theta, P)
+        if not isinstance(obs, torch.Tensor) or obs.dim() != 3 or not isinstance(meas, torch.Tensor) or meas.dim() != 3 or meas.shape[1] < 1 \
+                or meas.shape[1] % T or obs.shape[0] < 1:
+            raise ValueError(f"{what}: obs must be a tensor [K, N, {self.D}] and meas a tensor [K, M, {self.D}] with M a multiple of the {T} sets, "
+                             f"got {tuple(getattr(obs, 'shape', ()))} and {tuple(getattr(meas, 'shape', ()))}")
+        K, M = int(obs.shape[0]), int(meas.shape[1])
+        N, E, D, i32 = (2 * P + 1) * M, P * (P + 1) // 2 + P + 1, self.D, torch.int32
+        if N > 2 ** 31 - 1:
+            raise ValueError(f"{what}: (2 P + 1) M = {N} lanes exceed 2^31 - 1")
+        if not isinstance(constants, sysid.Os2riConstants):
+            raise ValueError(f"{what}: constants must be a sysid.Os2riConstants (sysid.constants() makes one), got {type(constants)}")
+        for name in sysid.CONSTANT_NAMES:
+            if not math.isfinite(getattr(constants, name)):
+                raise ValueError(f"{what}: constants.{name} must be finite, got {getattr(constants, name)}")
+        if constants.lam_min < 0.0 or not constants.diag_floor > 0.0:
+            raise ValueError(f"{what}: constants.lam_min must be >= 0 and constants.diag_floor > 0, got {constants.lam_min} and {constants.diag_floor}")
+        if any(t is None for t in (prec, theta_next, sums, counts)):
+            raise ValueError(f"{what}: prec, theta_next, sums and counts are required")
+        rows = self._sysid_state(what, state, T, P)
+        out_rows = self._sysid_state(what, state_new, T, P, "state_new")
+        inputs = ((obs, (K, N, D), None, "obs"), (meas, (K, M, D), None, "meas"), (done, (K, N), torch.uint8, "done"), (prec, (D,), None, "prec"),
+                  (theta, (T, P), None, "theta")) + rows
+        outputs = out_rows + ((theta_next, (T, P), None, "theta_next"), (cost, (T,), None, "cost"), (valid, (T,), i32, "valid"),
+                              (accepted, (T,), torch.uint8, "accepted"), (failed, (T,), i32, "failed"), (delta, (T, P), None, "delta"),
+                              (sums, (E * (M + T),), None, "sums"), (counts, (M + T,), i32, "counts"))
+        self._outs(what, inputs + outputs)
+        self._no_overlap(what, inputs, outputs)
+        _call(sysid, "os2ri_update", "os2ri_last_error", C.byref(self._layout()), P, T, M, K, hs, los, his, C.byref(constants), _ptr(obs), _ptr(meas),
+              _ptr(done), _ptr(prec), _ptr(theta), *[_ptr(t) for t in state], *[_ptr(t) for t in state_new], _ptr(theta_next), _ptr(cost),
+              _ptr(valid), _ptr(accepted), _ptr(failed), _ptr(delta), _ptr(sums), _ptr(counts), self._stream())
+
+    def sysid_update(self, obs, meas, prec, theta, state, *, h, lo, hi, constants=None, done=None, want_info: bool = True):
+        """One Levenberg-Marquardt step of T parameter sets (include/os2r_sysid.h: os2ri_update): obs [K, N, D] and done [K, N] are
+        what rollout(K, actions) returned for the lanes of sysid_perturb(theta, ...), as they lie on the device; meas [K, M, D]
+        the logged observations of the M segments, prec [D] the weights of the observation slots, state what sysid_init or the
+        last sysid_update returned; h, lo and hi are those of the sysid_perturb call; constants None is sysid.constants().
+        -> (state_new: seven new tensors as state; theta_next [T, P]: the point of the next sysid_perturb; info | None: (cost [T],
+        valid [T] int32: the segments that counted, accepted [T] uint8, failed [T] int32: 0 or the column + 1 at which the
+        factor of the damped system failed, delta [T, P]: the step))."""
+        what = "sysid_update"
+        P, _, _, _, _ = self._sysid_steps(what, None, h, lo, hi)
+        T = self._sysid_sets(what, theta, P)
+        if not isinstance(meas, torch.Tensor) or meas.dim() != 3 or meas.shape[1] < 1:
+            raise ValueError(f"{what}: meas must be a tensor [K, M, {self.D}], got {tuple(getattr(meas, 'shape', ()))}")
+        M, E, i32 = int(meas.shape[1]), P * (P + 1) // 2 + P + 1, torch.int32
+        state_new = (self._new(T, P), self._new(T), self._new(T, P, P), self._new(T, P), self._new(T), self._new(T, dtype=i32),
+                     self._new(T, dtype=i32))
+        theta_next, sums, counts = self._new(T, P), self._new(E * (M + T)), self._new(M + T, dtype=i32)
+        info = (self._new(T), self._new(T, dtype=i32), self._new(T, dtype=torch.uint8), self._new(T, dtype=i32), self._new(T, P)) if want_info \
+            else (None,) * 5
+        self.sysid_update_into(obs, meas, prec, theta, state, state_new, theta_next, sums, counts, h=h, lo=lo, hi=hi,
+                               constants=sysid.constants() if constants is None else constants, done=done, cost=info[0], valid=info[1],
+                               accepted=info[2], failed=info[3], delta=info[4])
+        return state_new, theta_next, info if want_info else None
